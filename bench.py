@@ -2,7 +2,17 @@
 """Benchmark: encode+decode round trip of the PQ+Huffman hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode ctx|noctx]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (value,
+ms_per_step, and the roofline of the assignment kernel from the HIP events that ride in the
+timed steps).  --dump-outputs DIR also writes what the last timed step returned (codes,
+decoded rows, stream, chunk index) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.  --full adds, after the timed
+steps: the other stages' event times from untimed steps of their own (`stages_ms`,
+`encode_read_roofline_frac`), the checks of the last batch (round trip, row-path re-encode,
+status words), `pcie_ms` and `cpu_baseline`.
 
 Workload (BASELINE.json configs[1], SIFT1M-shaped): per GPU 1,000,000 synthetic SIFT-like
 128-d fp32 vectors resident in HBM, M=8 sub-spaces, K=256 centroids (weak scaling: every
@@ -110,8 +120,20 @@ def parse(argv=None):
                          "by that chain's latency, so more, shorter chains decode faster: chunk "
                          "4 vs 8 measured 45 vs 58 us alone per 1M SIFT rows, 141 vs 247 Deep; "
                          "bench 2,976-3,008 vs 2,856-2,858 Mvec/s, Deep 1,538 vs 1,356)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the other stages' HIP-event times in untimed "
+                         "steps of their own (stages_ms, encode_read_roofline_frac), the checks of "
+                         "the last batch (round trip, row-path re-encode, status words), pcie_ms "
+                         "and cpu_baseline.  A plain run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (rank 0's "
+                         "shard) to DIR/<name>.npy: codes, decoded, stream, stream_bits, "
+                         "chunk_offsets[, chunk_prev]; float32 / float64, fixed seeded samples of "
+                         "the larger arrays (see dump_outputs)")
     ap.add_argument("--cpu-sample", type=int, default=200_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the cpu_baseline legs")
     ap.add_argument("--sched", choices=["lanes", "serial"], default="lanes",
                     help="'lanes': assignment + histogram on one stream, each batch's code "
                          "tables, encode and decode on one of --lanes streams (overlapped); "
@@ -141,10 +163,10 @@ def parse(argv=None):
                          "assignment stream, their reduce on the batch's table lane")
     ap.add_argument("--stage-events", choices=["after", "timed"], default="after",
                     help="per-stage HIP events other than the assignment's: recorded in extra "
-                         "untimed steps after the timed region (default: an event record is a "
-                         "packet on its stream, +2-3 %% when all ride in the timed steps), or "
-                         "inside the timed steps; the assignment's (the roofline kernel) are "
-                         "always recorded in the timed steps")
+                         "untimed steps after the timed region (default, and only with --full: an "
+                         "event record is a packet on its stream, +2-3 %% when all ride in the "
+                         "timed steps), or inside the timed steps; the assignment's (the roofline "
+                         "kernel) are always recorded in the timed steps")
     ap.add_argument("--encode-after", choices=["tables", "trees"], default="tables",
                     help="the encode waits for the batch's whole tables, or (trees) only for its "
                          "Huffman trees when they completed the encode tables (group builder), "
@@ -398,6 +420,55 @@ def pcie_ms(torch, x, codes, stream_bytes):
         torch.cuda.synchronize()
         out[name] = round((time.perf_counter() - t0) / 3 * 1e3, 3)
     return out
+
+
+DUMP_ROWS = 131_072       # sampled rows of codes / decoded, sampled chunks of the chunk index
+DUMP_BYTES = 4_194_304    # sampled bytes of the stream
+
+
+def _sample(n, size, seed):
+    """every index below n, or a fixed (seeded) sorted sample of about `size` of them"""
+    if n <= size:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size))
+
+
+def dump_outputs(torch, path, codes, part_major, dec, stream, bits, coff, cprev, pad=0):
+    """--dump-outputs: what the last timed step handed back, one .npy per array, every value
+    exact in its float type (at most ~42 MB in all):
+      codes          the assignment's PQ codes, rows x m (float32; --code-layout parts: gathered
+                     from the part-major buffer), DUMP_ROWS sampled rows of a larger batch
+      decoded        the decoder's output for the same rows (float32)
+      stream         the encoded stream's bytes, one per value (float32), DUMP_BYTES sampled
+                     positions of a longer stream
+      stream_bits    the stream's length in bits (float64, one value)
+      chunk_offsets  the decode index: each chunk's bit offset (float64), DUMP_ROWS sampled chunks
+      chunk_prev     context mode: each of those chunks' context row (float32)
+    The samples depend only on the sizes, so two runs with the same arguments write the same
+    positions."""
+    os.makedirs(path, exist_ok=True)
+    dev = dec.device
+
+    def host(t, typ=np.float32):
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:     # (u16 codes live in int16 tensors)
+            a = a.view(np.uint16)
+        return np.ascontiguousarray(a.astype(typ))
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+    rows = torch.from_numpy(_sample(dec.shape[0], DUMP_ROWS, 0x5EED)).to(dev)
+    save("codes", host(codes[:, rows].T if part_major else codes[rows]))
+    save("decoded", host(dec[rows]))
+    nbytes = (bits + 7) // 8 + pad   # (pad: a shard's stream starts inside its first bytes)
+    where = torch.from_numpy(_sample(nbytes, DUMP_BYTES, 0x5EED + 1)).to(dev)
+    save("stream", host(stream[:nbytes][where]))
+    save("stream_bits", np.array([bits], dtype=np.float64))
+    chunks = torch.from_numpy(_sample(coff.shape[0], DUMP_ROWS, 0x5EED + 2)).to(dev)
+    save("chunk_offsets", host(coff[chunks], np.float64))
+    if cprev is not None:
+        save("chunk_prev", host(cprev[chunks]))
 
 
 def main():
@@ -982,7 +1053,13 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     state["timed"] = False
-    if args.stage_events == "after":
+    if args.dump_outputs and rank == 0:   # the last timed step's own buffers, before anything reruns
+        s_t, j_t = state["last"]
+        w_t = state["last_w"]
+        # (world > 1: the shard's first bit lies inside the buffer's first 8 bytes, as in --dump)
+        dump_outputs(torch, args.dump_outputs, codes[s_t], pm, dec[j_t], out[w_t],
+                     int(tot_dev[w_t].item()), coff[w_t], cprev[w_t], pad=8 if multi else 0)
+    if args.full and args.stage_events == "after":
         # the other stages' events, in untimed steps of the same schedule (an event record is
         # a packet on its stream: inside the timed steps they would cost stream time)
         ev_pool.extend((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -1010,15 +1087,20 @@ def main():
     s_last, j_last = state["last"]
     w_last = state["last_w"]
 
-    # correctness after timing (not timed): exact round trip of the last batch, status words
-    for t in tabs:
-        t.status()
-    for c in elanes:
-        codec.decode_status(c)
-        codec.encode_status(c)
-    rows_last = codec.transpose_codes(ctx, codes[s_last], n) if pm else codes[s_last]
-    assert torch.equal(dec[j_last], rows_last), "round trip mismatch"
-    if world == 1 and not serial:
+    # the last batch's codes as rows: for --full's checks and PCIe figures, and for --dump
+    rows_last = None
+    if args.full or args.dump:
+        rows_last = codec.transpose_codes(ctx, codes[s_last], n) if pm else codes[s_last]
+    # --full: correctness after timing (not timed): exact round trip of the last batch, status
+    # words
+    if args.full:
+        for t in tabs:
+            t.status()
+        for c in elanes:
+            codec.decode_status(c)
+            codec.encode_status(c)
+        assert torch.equal(dec[j_last], rows_last), "round trip mismatch"
+    if args.full and world == 1 and not serial:
         # the last batch's stream, re-encoded from its rows by the row-major encoder
         # (pqh_encode_write, the path tests/test_gpu_fullsize.py pins to the oracle on all 1M
         # rows) with the same tables: every stream byte, the bit count and the chunk index
@@ -1039,7 +1121,7 @@ def main():
         if ctxm:
             assert torch.equal(cprev[w_last], ref_prev), "chunk context rows != row-path re-encode"
         del ref_out, ref_coff, ref_prev, ref_tot
-    if lib_shard:   # every rank's pqh_shard_encode_write succeeded (no sentinel length)
+    if args.full and lib_shard:   # every rank's pqh_shard_encode_write succeeded (no sentinel)
         shard.status(elanes[j_last], offs[w_last])
         for j, sm in enumerate(shard_min):   # ... for every batch, not only the last
             assert int(sm.item()) >= 0, f"a rank's shard encode failed (encode stream {j})"
@@ -1066,13 +1148,20 @@ def main():
                      x=np.concatenate([p["x"] for p in allp]), cent=cent)
 
     if rank == 0:
-        t_assign = acc["assign"] / args.steps
+        # the other stages were timed: in --full's untimed steps, or inside the timed ones
+        have_stages = args.full or args.stage_events == "timed"
+        # (a plain run with --assign-event-every 0 records no assignment events: no roofline times)
+        t_assign = acc["assign"] / args.steps or None
         vec_read, vec_write = 4 * d, m * code_bytes
-        achieved = (vec_read + vec_write) * n / t_assign / 1e9
+        achieved = (vec_read + vec_write) * n / t_assign / 1e9 if t_assign else None
         akern = ASSIGN_KERNEL[args.config]
         traffic, traffic_src, prof_avg_us = pmc_traffic(akern, profile_tag(args.config, args.sort, args.vectors))
         t_enc = (acc["assign"] + acc["hist"] + acc["codebook"] + acc["lut"] + acc["encode"]) / args.steps
-        tf = 2.0 * k * d * n / t_assign / 1e12   # algorithmic: 2 K D flop per vector
+        # algorithmic: 2 K D flop per vector
+        tf = 2.0 * k * d * n / t_assign / 1e12 if t_assign else None
+
+        def rnd(v, digits):
+            return None if v is None else round(v, digits)
         workload = {
             "sift": f"SIFT1M-shaped: {n:,} x 128-d fp32 per GPU, M=8, K=256, ",
             "deep": f"Deep1B-style (BASELINE configs[3]): {n:,} x 96-d unit-norm fp32 per GPU, "
@@ -1096,6 +1185,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "device_warmup_ms": round(dw_ms, 1),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
@@ -1152,15 +1242,15 @@ def main():
                                              "schedule it shares the SIMDs with the side "
                                              "kernels -- not HBM (traffic 1.05x the "
                                              "algorithmic bytes)",
-                         "mfma_tflops_algorithmic": round(tf, 1),
+                         "mfma_tflops_algorithmic": rnd(tf, 1),
                          # of the dense bf16 peak (~2.5 PF/s); each fp32 product costs two or
                          # three bf16 MFMA passes (the hi/lo split), so issued MFMA work is 2-3x
-                         "mfma_frac_bf16_dense": round(tf / 2500.0, 4),
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                         "mfma_frac_bf16_dense": rnd(tf and tf / 2500.0, 4),
+                         "achieved": rnd(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": rnd(achieved and achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "traffic_source": traffic_src,
                          "bytes_per_vector": vec_read + vec_write,
-                         "avg_ms": round(t_assign * 1e3, 4),
+                         "avg_ms": rnd(t_assign and t_assign * 1e3, 4),
                          # rocprofv3 kernel-trace average of this bench command (dispatch
                          # begin -> end); avg_ms above is HIP events around the launch on its
                          # stream, which also count the wait for CUs held by the lanes
@@ -1172,17 +1262,7 @@ def main():
                          "alone_avg_ms": (round(sum(alone) / len(alone), 4) if alone else None),
                          "alone_frac": (round((vec_read + vec_write) * n / (sum(alone) / len(alone) * 1e-3)
                                               / 1e9 / HBM_PEAK_GBS, 4) if alone else None)},
-            "stages_ms": {s: round(v / args.steps * 1e3, 4) for s, v in acc.items()
-                          if (s != "sort" or args.sort) and (s != "lut" or lut_a)},
-            "stages_note": ("per-stage HIP-event times on their own streams (the assignment's "
-                            "over the timed steps, the others over untimed steps of the same "
-                            "schedule after them, --stage-events)" +
-                            ("" if serial else "; the stages of consecutive batches run "
-                             "concurrently, so they sum to more than ms_per_step")),
-            # SURVEY 8d: encode-side HBM-read roofline = 512 B/vec x N / t_encode / 8 TB/s, with
-            # t_encode = the summed encode-side stage times of one batch (latency view) and,
-            # for the throughput view, the whole round-trip step time
-            "encode_read_roofline_frac": round(vec_read * n / t_enc / 1e9 / HBM_PEAK_GBS, 4),
+            # SURVEY 8d, the throughput view: 512 B/vec x N over the whole round-trip step time
             "roundtrip_read_roofline_frac": round(
                 vec_read * n * world * args.steps / elapsed / 1e9 / HBM_PEAK_GBS / world, 4),
             "host_issue_ms_per_step": round(t_issue / args.steps * 1e3, 3),
@@ -1201,13 +1281,24 @@ def main():
                 bits_per_vec / 8 + (8 + (m * code_bytes if ctxm else 0)) / args.chunk, 3),
             "rerank_fraction": round(rerank / (n * m), 6),
         }
-        if world == 1:
+        if have_stages:
+            res["stages_ms"] = {s: round(v / args.steps * 1e3, 4) for s, v in acc.items()
+                                if (s != "sort" or args.sort) and (s != "lut" or lut_a)}
+            res["stages_note"] = ("per-stage HIP-event times on their own streams (the "
+                                  "assignment's over the timed steps, the others over untimed "
+                                  "steps of the same schedule after them, --stage-events)" +
+                                  ("" if serial else "; the stages of consecutive batches run "
+                                   "concurrently, so they sum to more than ms_per_step"))
+            # SURVEY 8d: encode-side HBM-read roofline = 512 B/vec x N / t_encode / 8 TB/s, with
+            # t_encode = the summed encode-side stage times of one batch (latency view)
+            res["encode_read_roofline_frac"] = round(vec_read * n / t_enc / 1e9 / HBM_PEAK_GBS, 4)
+        if args.full and world == 1:
             # (after the timed region, on a scratch copy of a 1M-row slice)
             r1 = min(n, 1_000_000)
             res["pcie_ms"] = pcie_ms(torch, x[:r1].clone(), rows_last[:r1],
                                      (bits_per_vec * r1 + 7) // 8)
             res["pcie_ms"]["rows"] = r1
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sample = max(1000, args.cpu_sample * 256 // k)   # ~the same CPU time at any K
             xh = x[:sample].cpu().numpy()
             res["cpu_baseline"] = cpu_baseline(xh, cent, ctxm, sample, args.sort)

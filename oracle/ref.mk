@@ -45,14 +45,16 @@ $(OUT)/huffman_decoder_O0: $(REF)/huffman_decoder.c $(LIBSRC) $(TREESRC) | $(OUT
 # huffman_encoder.c / huffman_decoder.c (+ mst.c, dsu.c: the forest loader libpqh does not
 # replace) compiled against include/*.h (`-I-`: quote includes skip the source's own
 # directory, so huffman.h, bitstream.h, stats.h, misc.h, vecs_io.h come from include/),
-# linked with -lpqh instead of the reference's library objects.
+# linked with -lpqh instead of the reference's library objects.  The run path is relative to
+# the tool ($ORIGIN, as pq_huffman_amd/bin's), so a tree that is moved or copied after the
+# build still finds its own libpqh.so.
 PQH_LIB := pq_huffman_amd/lib
 CFLAGS_RELINK := -std=c99 -O2 -w -Iinclude -I- -I$(REF)
 $(OUT)/relink:
 	mkdir -p $(OUT)/relink
 $(OUT)/relink/%: $(REF)/%.c $(TREESRC) $(PQH_LIB)/libpqh.so | $(OUT)/relink
 	$(CC) $(CFLAGS_RELINK) -o $@ $< $(TREESRC) -L$(PQH_LIB) -lpqh \
-	    -Wl,-rpath,$(abspath $(PQH_LIB)) -lm
+	    -Wl,-rpath,'$$ORIGIN/../../../$(PQH_LIB)' -lm
 
 # embedded `#ifdef _X_TEST` mains (src/bitstream.c:196, huffman_encode.c:280,
 # huffman_decode.c:193, huffman_codebook.c:145); not built by the reference Makefile

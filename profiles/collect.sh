@@ -15,11 +15,11 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 300 python3 "$R/bench.py" --no-cpu-baseline "$@" > "$OUT/bench.log" 2>&1
+timeout -k 10 300 python3 "$R/bench.py" --full --no-cpu-baseline "$@" > "$OUT/bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv \
-    -- python3 "$R/bench.py" --no-cpu-baseline "$@" > "$OUT/kt.log" 2>&1
+    -- python3 "$R/bench.py" --full --no-cpu-baseline "$@" > "$OUT/kt.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv \
-    -- python3 "$R/bench.py" --no-cpu-baseline --steps 3 --warmup 1 "$@" > "$OUT/fetch.log" 2>&1
+    -- python3 "$R/bench.py" --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > "$OUT/fetch.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o write --output-format csv \
-    -- python3 "$R/bench.py" --no-cpu-baseline --steps 3 --warmup 1 "$@" > "$OUT/write.log" 2>&1
+    -- python3 "$R/bench.py" --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > "$OUT/write.log" 2>&1
 echo "profiles collected under $OUT"

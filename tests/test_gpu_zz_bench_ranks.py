@@ -43,7 +43,8 @@ def test_two_rank_rehearsal_stitched_stream(oracle, tmp_path, mode, path):
            *_LAUNCH,
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
            "--one-device", "--vectors", "30001", "--steps", "3", "--warmup", "1",
-           "--mode", mode, "--no-cpu-baseline", "--dump", str(dump), "--shard-path", path]
+           "--mode", mode, "--full", "--no-cpu-baseline", "--dump", str(dump),
+           "--shard-path", path]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, run_fail_msg(r)
     d = np.load(dump, allow_pickle=False)
@@ -67,7 +68,7 @@ def test_one_rank_rccl_rehearsal_stream(oracle, tmp_path, groups):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            *_LAUNCH,
            os.path.join(ROOT, "bench.py"), "--dist-rehearse", "--shard-groups", groups,
-           "--vectors", "30001", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
+           "--vectors", "30001", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--dump", str(dump)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, run_fail_msg(r)
@@ -90,7 +91,7 @@ def test_one_rank_bench_stream(oracle, tmp_path, config, mode):
     (src/pq_encoder.c:270-272, src/huffman_encoder.c:207-238)."""
     dump = tmp_path / "dump.npz"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--mode", mode,
-           "--vectors", "30001", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--vectors", "30001", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--device-warmup-ms", "0", "--dump", str(dump)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, run_fail_msg(r)
@@ -103,3 +104,39 @@ def test_one_rank_bench_stream(oracle, tmp_path, config, mode):
     assert int(d["bits"]) == bits
     assert d["stream"].tobytes() == want
 
+
+def test_plain_bench_dump_outputs(oracle, tmp_path):
+    """a plain run (no --full): the line carries the headline fields for `--steps` timed steps
+    and none of --full's figures, and --dump-outputs writes the last timed step's arrays as
+    float32 / float64 .npy, at most 64 MB in all: at this size every row, byte and chunk, so
+    the codes equal the oracle's assignment, `decoded` the codes, the stream and its length
+    the oracle's encoding, and the chunk index each chunk's previous row."""
+    import json
+    dump, outs = tmp_path / "dump.npz", tmp_path / "outs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--vectors", "30001",
+           "--steps", "3", "--warmup", "1", "--device-warmup-ms", "0", "--dump", str(dump),
+           "--dump-outputs", str(outs)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, run_fail_msg(r)
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "Mvec/s"
+    # value = vectors / step time (both rounded in the line: 3 and 2 decimals)
+    rel = 0.0006 / line["ms_per_step"] + 0.006 / line["value"]
+    assert abs(line["value"] * line["ms_per_step"] * 1e3 / 30001 - 1) <= rel
+    for key in ("metric", "higher_is_better", "dtype"):
+        assert key in line
+    for key in ("cpu_baseline", "pcie_ms", "stages_ms"):
+        assert key not in line
+    a = {f[:-4]: np.load(outs / f, allow_pickle=False) for f in sorted(os.listdir(outs))}
+    assert set(a) == {"codes", "decoded", "stream", "stream_bits", "chunk_offsets", "chunk_prev"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    d = np.load(dump, allow_pickle=False)
+    want, _ = oracle.pq_assign(d["x"], d["cent"], threads=0)
+    assert np.array_equal(a["codes"], want) and np.array_equal(a["decoded"], want)
+    stream, bits = oracle.encode(want, oracle.build_codebooks(want, 256, True))
+    assert int(a["stream_bits"][0]) == bits
+    assert a["stream"].astype(np.uint8).tobytes() == stream[:(bits + 7) // 8]
+    assert a["chunk_offsets"].shape == ((30001 + 3) // 4,) and a["chunk_offsets"][0] == 0
+    assert np.all(np.diff(a["chunk_offsets"]) > 0) and a["chunk_offsets"][-1] < bits
+    assert np.array_equal(a["chunk_prev"][1:], want[3:-1:4])

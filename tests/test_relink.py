@@ -23,6 +23,12 @@ pytestmark = pytest.mark.skipif(
     not (os.path.isdir("/root/reference/src") and os.path.exists(os.path.join(RELINK, "huffman_encoder"))),
     reason="needs the reference sources (build container) and the relinked tools")
 
+# the relinked tools load THIS tree's libpqh.so, wherever oracle/_ref was built or is kept
+# (its run path is relative to the tool, which a linked or carried-over oracle/_ref defeats)
+_ENV = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+    [os.path.join(ROOT, "pq_huffman_amd", "lib")]
+    + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]))
+
 FILES = ["huffman_codebooks.bin", "huffman_indices.bin", "huffman_stats.txt"]
 TREE_FILES = FILES + ["huffman_children_codebooks.bin", "huffman_children.bin",
                       "huffman_children_stats.txt"]
@@ -35,7 +41,7 @@ def _encode(tool_dir, codes, flags, work):
     os.makedirs(out, exist_ok=True)
     datagen.write_vecsl(pq + "pq_indices.bvecsl", codes)
     r = subprocess.run([os.path.join(tool_dir, "huffman_encoder"), pq, out, str(codes.shape[1])]
-                       + flags, capture_output=True, text=True, timeout=120)
+                       + flags, capture_output=True, text=True, timeout=120, env=_ENV)
     assert r.returncode == 0, r.stderr
     return out, r.stdout
 
@@ -43,7 +49,7 @@ def _encode(tool_dir, codes, flags, work):
 def _decode(tool_dir, enc_dir, flags, work):
     outf = os.path.join(work, "decoded.bin")
     r = subprocess.run([os.path.join(tool_dir, "huffman_decoder"), enc_dir, "--output-file", outf]
-                       + flags, capture_output=True, text=True, timeout=120)
+                       + flags, capture_output=True, text=True, timeout=120, env=_ENV)
     assert r.returncode == 0, r.stderr
     return open(outf, "rb").read(), r.stdout
 

@@ -10,7 +10,7 @@ for r in 1 2; do
       if [[ $w =~ ^[A-Z_0-9]+= ]]; then E+=("$w"); else F="$F $w"; fi
     done
     for K in 20 100; do
-      env "${E[@]}" timeout -k 10 200 python bench.py --steps $K --warmup 5 --no-cpu-baseline $F > "$OUT/$L.$K.$r.log" 2>&1 || { tail -5 "$OUT/$L.$K.$r.log"; exit 1; }
+      env "${E[@]}" timeout -k 10 200 python bench.py --steps $K --warmup 5 --full --no-cpu-baseline $F > "$OUT/$L.$K.$r.log" 2>&1 || { tail -5 "$OUT/$L.$K.$r.log"; exit 1; }
       python - "$OUT/$L.$K.$r.log" "$L" <<'PY'
 import json, sys
 for line in open(sys.argv[1]):

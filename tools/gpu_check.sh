@@ -8,7 +8,7 @@ tail -1 $OUT/tests.log
 for i in 1 2; do
   for K in 200 20; do
     W=10; [ $K = 20 ] && W=5
-    timeout -k 10 300 python bench.py --steps $K --warmup $W --no-cpu-baseline > $OUT/b$K.$i.log 2>&1 || { tail $OUT/b$K.$i.log; exit 1; }
+    timeout -k 10 300 python bench.py --steps $K --warmup $W --full --no-cpu-baseline > $OUT/b$K.$i.log 2>&1 || { tail $OUT/b$K.$i.log; exit 1; }
     echo "K=$K $(grep -o '"value": [0-9.]*' $OUT/b$K.$i.log) $(grep -o '"stages_ms": {[^}]*}' $OUT/b$K.$i.log)"
   done
 done

@@ -12,8 +12,10 @@ done
 for rep in 1 2; do
 for c in 2 1; do
   for a in "--steps 200 --warmup 20" "--config deep --steps 100 --warmup 10"; do
-    PQH_DEC_CHAINS=$c timeout -k 10 300 python bench.py $a --no-cpu-baseline > gpurun_out/dec/b.log 2>&1 || { tail gpurun_out/dec/b.log; exit 1; }
-    echo "chains=$c [$a] $(grep -o '"value": [0-9.]*' gpurun_out/dec/b.log) $(grep -o '"stages_ms": {[^}]*}' gpurun_out/dec/b.log)"
+    B=$(mktemp)   # the bench line (stage times: --full)
+    PQH_DEC_CHAINS=$c timeout -k 10 300 python bench.py $a --full --no-cpu-baseline > $B 2>&1 || { tail $B; exit 1; }
+    echo "chains=$c [$a] $(grep -o '"value": [0-9.]*' $B) $(grep -o '"stages_ms": {[^}]*}' $B)"
+    rm -f $B
   done
 done
 done

@@ -11,7 +11,7 @@ for i in 1 2; do
   for v in "${V[@]}"; do
     L=""; [ "$v" != in-tree ] && L=$GRAFT_REPO_ROOT/pq_huffman_amd/lib/variants/$v/libpqh.so
     env ${L:+PQH_LIB=$L} timeout -k 10 200 python tools/bench_assign.py 20 deep 2>&1 | grep -v amdgpu.ids | sed "s/^/$v /" || exit 1
-    env ${L:+PQH_LIB=$L} timeout -k 10 300 python bench.py --config deep --steps 100 --warmup 10 --no-cpu-baseline > $OUT/$v.$i.log 2>&1 || { tail $OUT/$v.$i.log; exit 1; }
+    env ${L:+PQH_LIB=$L} timeout -k 10 300 python bench.py --config deep --steps 100 --warmup 10 --full --no-cpu-baseline > $OUT/$v.$i.log 2>&1 || { tail $OUT/$v.$i.log; exit 1; }
     echo "$v bench $(grep -o '"value": [0-9.]*' $OUT/$v.$i.log) $(grep -o '"alone_avg_ms": [0-9.]*' $OUT/$v.$i.log) $(grep -o '"stages_ms": {[^}]*}' $OUT/$v.$i.log)"
   done
 done

@@ -6,7 +6,7 @@ for r in 1 2; do
   for K in ${@:-20}; do
     timeout -k 10 200 python bench.py --steps $K --warmup 5 --no-cpu-baseline > $O/one.$K.$r.log 2>&1 || { tail $O/one.$K.$r.log; exit 1; }
     echo "one K=$K $(grep -o '"value": [0-9.]*' $O/one.$K.$r.log)"
-    timeout -k 10 200 python -m torch.distributed.run --standalone --local-addr=127.0.0.1 --nnodes=1 --nproc-per-node=1 bench.py --dist-rehearse --steps $K --warmup 5 --no-cpu-baseline ${DFLAGS:-} > $O/reh.$K.$r.log 2>&1 || { tail $O/reh.$K.$r.log; exit 1; }
+    timeout -k 10 200 python -m torch.distributed.run --standalone --local-addr=127.0.0.1 --nnodes=1 --nproc-per-node=1 bench.py --dist-rehearse --steps $K --warmup 5 --full --no-cpu-baseline ${DFLAGS:-} > $O/reh.$K.$r.log 2>&1 || { tail $O/reh.$K.$r.log; exit 1; }
     echo "rehearse K=$K $(grep -o '"value": [0-9.]*' $O/reh.$K.$r.log) $(grep -o '"stages_ms": {[^}]*}' $O/reh.$K.$r.log)"
   done
 done

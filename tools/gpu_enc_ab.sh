@@ -10,6 +10,8 @@ for impl in tiled onepass; do
   PQH_ENC_IMPL=$impl timeout -k 10 300 python tools/bench_encdec.py --config sift --rows 16000000 --reps 5 2>&1 | grep -v amdgpu.ids | sed "s/^/$impl /" || exit 1
 done
 for impl in tiled onepass; do
-  PQH_ENC_IMPL=$impl timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline > gpurun_out/enc/b200_$impl.log 2>&1 || { tail gpurun_out/enc/b200_$impl.log; exit 1; }
-  echo "$impl $(grep -o '"value": [0-9.]*' gpurun_out/enc/b200_$impl.log) $(grep -o '"stages_ms": {[^}]*}' gpurun_out/enc/b200_$impl.log)"
+  B=$(mktemp)   # the bench line (stage times: --full)
+  PQH_ENC_IMPL=$impl timeout -k 10 300 python bench.py --steps 200 --warmup 20 --full --no-cpu-baseline > $B 2>&1 || { tail $B; exit 1; }
+  echo "$impl $(grep -o '"value": [0-9.]*' $B) $(grep -o '"stages_ms": {[^}]*}' $B)"
+  rm -f $B
 done

@@ -7,6 +7,6 @@ A=$1; shift
 i=0
 for e in "$@"; do
   i=$((i+1)); [ "$e" = "-" ] && e=""
-  timeout -k 10 300 env $e python bench.py $A --no-cpu-baseline > $OUT/r$i.log 2>&1 || { tail $OUT/r$i.log; exit 1; }
+  timeout -k 10 300 env $e python bench.py $A --full --no-cpu-baseline > $OUT/r$i.log 2>&1 || { tail $OUT/r$i.log; exit 1; }
   echo "[$e] $(grep -o '"value": [0-9.]*' $OUT/r$i.log) $(grep -o '"stages_ms": {[^}]*}' $OUT/r$i.log)"
 done

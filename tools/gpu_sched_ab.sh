@@ -8,6 +8,6 @@ i=0
 for a in "${SETS[@]}"; do
   i=$((i+1))
   args=$(echo "$a" | tr ',' ' ')
-  timeout -k 10 400 env $ENVV python bench.py $args --no-cpu-baseline > $OUT/run$i.log 2>&1 || { tail $OUT/run$i.log; exit 1; }
+  timeout -k 10 400 env $ENVV python bench.py $args --full --no-cpu-baseline > $OUT/run$i.log 2>&1 || { tail $OUT/run$i.log; exit 1; }
   echo "[$args] $(grep -o '"value": [0-9.]*' $OUT/run$i.log) $(grep -o '"stages_ms": {[^}]*}' $OUT/run$i.log)"
 done

@@ -5,7 +5,7 @@ set -e
 mkdir -p gpurun_out/prio
 run() {   # name, env...
     local name=$1; shift
-    env "$@" timeout -k 10 120 python bench.py --steps 200 --warmup 5 --no-cpu-baseline \
+    env "$@" timeout -k 10 120 python bench.py --steps 200 --warmup 5 --full --no-cpu-baseline \
         > gpurun_out/prio/$name.log 2>&1
     python - "$name" <<'PY'
 import json, sys
