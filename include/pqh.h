@@ -285,9 +285,51 @@ int pqh_decode(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_str
                unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
                const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
                void* d_codes);
-/* Synchronises; PQH_ERR_CORRUPT if a pqh_decode / pqh_decode_tree on this context since
- * the last call met an invalid code (sticky until read here, like pqh_encode_status). */
+/* Synchronises; PQH_ERR_CORRUPT if a pqh_decode / pqh_decode_tree / random-access decode
+ * (below) on this context since the last call met an invalid code (sticky until read here,
+ * like pqh_encode_status); PQH_ERR_ARG if none did but a pqh_decode_select /
+ * pqh_fetch_vectors was given a row id outside [0, n). */
 int pqh_decode_status(pqh_ctx_t* ctx);
+
+/* ---- random access through the chunk index (huffman_decoder.c:211-255 and
+ *      huffman_decode.c:137-191 for the rows asked for only) --------------------------
+ * The reference decoder reads a stream from its first bit; the chunk index lets a row be
+ * reached from the start of its chunk: bit offset d_chunk_offsets[v / C], context
+ * d_chunk_prev[v / C] (the raw first row for chunk 0 when raw_first), then the rows of the
+ * chunk up to v.  Stream, index and raw_first are pqh_decode's arguments (so a shard written
+ * with d_prev_row, raw_first = 0, is addressed by its own rows 0 ... n - 1); stream_bytes is
+ * the readable length in whole 32-bit words, and nothing is read outside it.  The shapes of
+ * pqh_decode: m <= 16 parts (else PQH_ERR_UNSUPPORTED), K <= 4096, context or not, any
+ * C >= 1.  Asynchronous; errors are reported by pqh_decode_status: an invalid code, a chunk
+ * offset or a symbol past stream_bytes * 8 bits is PQH_ERR_CORRUPT (the rows concerned are
+ * zeroed), which takes precedence over a bad id.  count == 0 returns PQH_OK and launches
+ * nothing.  Tree-mode streams (pqh_decode_tree) are out of scope: there a row's context is
+ * its parent, not its predecessor, so the chunk index does not lead to it. */
+/* d_codes[q] = row d_ids[q] of the stream, for q < count: one lane per id, ids in any order
+ * and repeated at will (device int64).  An id outside [0, n) gives a zero row and
+ * PQH_ERR_ARG from pqh_decode_status. */
+int pqh_decode_select(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                      unsigned long long stream_bytes, long long n, int raw_first,
+                      int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                      const void* d_chunk_prev, const long long* d_ids, long long count,
+                      void* d_codes /* [count][m] */);
+/* d_codes = rows [first, first + count) of the stream; first need not be a multiple of C.
+ * One lane per chunk: the whole chunks of the range run pqh_decode's kernels, the cut ones
+ * at its ends store only their rows inside the range.  first < 0 or first + count > n
+ * returns PQH_ERR_ARG at once. */
+int pqh_decode_range(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                     unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
+                     const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
+                     long long first, long long count, void* d_codes /* [count][m] */);
+/* pqh_decode_select fused with pqh_pq_reconstruct: d_out[q] = concat_i c[i][code_i] of row
+ * d_ids[q] in fp32, rows ld_out floats apart (the floats between rows are left alone); the
+ * codes are not written to memory.  pq and t must agree in m and K.  A bad id gives a row
+ * of zeros. */
+int pqh_fetch_vectors(pqh_ctx_t* ctx, const pqh_tables_t* t, const pqh_pq_t* pq,
+                      const unsigned char* d_stream, unsigned long long stream_bytes, long long n,
+                      int raw_first, int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                      const void* d_chunk_prev, const long long* d_ids, long long count,
+                      float* d_out, long long ld_out);
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by
  * the reference encoder) with a sequential table walk on the HOST copy of the stream
  * (index building only; the symbols themselves are decoded on the GPU). */
@@ -561,6 +603,16 @@ int pqh_decode_tree_files(const char* in_prefix, unsigned char** codes_out, long
  * (n x m host buffer, n from the file header). */
 int pqh_decode_files(const char* in_prefix, unsigned char** codes_out, long long* n_out,
                      int* m_out);
+/* Rows [first, first + count) of huffman_indices.bin under in_prefix, in stream order (the
+ * encoder's order: sorted unless it ran with sort = 0), into a malloc'd count x m host buffer
+ * (huffman_decoder.c:211-255 for those rows only).  Reads the code books, the sidecar's index
+ * entries of the range's chunks and only those chunks' bytes of the stream, and decodes them
+ * with pqh_decode_range.  The sidecar huffman_chunks.bin is required: without it (or with one
+ * that does not match the stream) the call returns PQH_ERR_ARG and names the file on stderr --
+ * there is no fall-back to a full decode.  A range outside the file's rows, or count <= 0, is
+ * PQH_ERR_ARG.  Non-tree streams only. */
+int pqh_decode_files_range(const char* in_prefix, long long first, long long count,
+                           unsigned char** codes_out, int* m_out);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,10 @@ SIGNATURES = [
     ("pqh_encode_write_parts", I, [P, P, P, LL, LL, I, P, ULL, P, ULL, I, P, P, P]),
     ("pqh_transpose_codes", I, [P, P, LL, LL, I, I, P]),
     ("pqh_decode", I, [P, P, P, ULL, LL, I, I, P, P, P]),
+    ("pqh_decode_select", I, [P, P, P, ULL, LL, I, I, P, P, P, LL, P]),
+    ("pqh_decode_range", I, [P, P, P, ULL, LL, I, I, P, P, LL, LL, P]),
+    ("pqh_fetch_vectors", I, [P, P, P, P, ULL, LL, I, I, P, P, P, LL, P, LL]),
+    ("pqh_decode_files_range", I, [S, LL, LL, P, P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

@@ -64,6 +64,12 @@ class Context:
 
     def __init__(self, device: int = 0, stream=None, cus: int = 0, complement: bool = False):
         torch = _torch()
+        # Tables and PQ objects free their device memory through the context they were made
+        # with (pqh_tables_destroy / pqh_pq_destroy synchronise its stream), so the context
+        # is destroyed only after the last of them: close() waits for _deps to reach 0.
+        # Finalisers of a garbage cycle run in any order; this keeps that order harmless.
+        self._deps = 0
+        self._closing = False
         self.device = device
         torch.cuda.set_device(device)
         self.ptr = ctypes.c_void_p()
@@ -104,7 +110,18 @@ class Context:
     def last_error(self) -> str:
         return (lib().pqh_ctx_last_error(self.ptr) or b"").decode()
 
+    def _retain(self) -> None:
+        self._deps += 1
+
+    def _release(self) -> None:
+        self._deps -= 1
+        if self._closing and self._deps <= 0:
+            self.close()
+
     def close(self) -> None:
+        if self._deps > 0:      # destroyed when the last Tables / PQ made with it closes
+            self._closing = True
+            return
         if self.ptr:
             lib().pqh_ctx_destroy(self.ptr)
             self.ptr = ctypes.c_void_p()
@@ -126,6 +143,7 @@ class PQ:
         self.ptr = ctypes.c_void_p()
         check(lib().pqh_pq_create(ctx.ptr, _ptr(c), self.m, self.k, self.dsub,
                                   ctypes.byref(self.ptr)), "pqh_pq_create")
+        ctx._retain()
 
     @property
     def code_dtype(self):
@@ -181,6 +199,7 @@ class PQ:
         if self.ptr:
             lib().pqh_pq_destroy(self.ptr)
             self.ptr = ctypes.c_void_p()
+            self.ctx._release()
 
     def __del__(self):
         try:
@@ -287,6 +306,7 @@ class Tables:
         st = lib().pqh_tables_alloc(ctx.ptr, m, k, int(context), ctypes.byref(self.ptr))
         if st:
             raise PqhError(st, "pqh_tables_alloc: " + ctx.last_error())
+        ctx._retain()
 
     @classmethod
     def from_codebooks(cls, ctx: Context, cbs: "Codebooks") -> "Tables":
@@ -353,6 +373,7 @@ class Tables:
         if self.ptr:
             lib().pqh_tables_destroy(self.ptr)
             self.ptr = ctypes.c_void_p()
+            self.ctx._release()
 
     def __del__(self):
         try:
@@ -534,6 +555,49 @@ def decode(ctx: Context, tables: Tables, enc: Encoded, out=None):
     check(lib().pqh_decode(ctx.ptr, tables.ptr, _ptr(enc.stream), enc.stream.numel(), enc.n,
                            enc.raw_first, enc.chunk_vectors, _ptr(enc.chunk_offsets),
                            _ptr(enc.chunk_prev), _ptr(out)), "pqh_decode")
+    return out
+
+
+def _index_args(enc: Encoded):
+    """the stream and chunk-index arguments every decode call takes, in pqh.h order"""
+    return (_ptr(enc.stream), enc.stream.numel(), enc.n, enc.raw_first, enc.chunk_vectors,
+            _ptr(enc.chunk_offsets), _ptr(enc.chunk_prev))
+
+
+def decode_rows(ctx: Context, tables: Tables, enc: Encoded, ids, out=None):
+    """rows `ids` (device int64, any order, repeats allowed) of the stream, out[q] = row
+    ids[q], without decoding the rest (pqh_decode_select).  Async; an id outside [0, n) gives
+    a zero row and decode_status raises PQH_ERR_ARG."""
+    torch = _torch()
+    dt = torch.uint8 if tables.k <= 256 else torch.int16
+    if out is None:
+        out = torch.empty((ids.numel(), tables.m), dtype=dt, device=enc.stream.device)
+    check(lib().pqh_decode_select(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(ids), ids.numel(),
+                                  _ptr(out)), "pqh_decode_select")
+    return out
+
+
+def decode_range(ctx: Context, tables: Tables, enc: Encoded, first: int, count: int, out=None):
+    """rows [first, first + count) of the stream (pqh_decode_range); async."""
+    torch = _torch()
+    dt = torch.uint8 if tables.k <= 256 else torch.int16
+    if out is None:
+        out = torch.empty((count, tables.m), dtype=dt, device=enc.stream.device)
+    check(lib().pqh_decode_range(ctx.ptr, tables.ptr, *_index_args(enc), first, count, _ptr(out)),
+          "pqh_decode_range")
+    return out
+
+
+def fetch(ctx: Context, tables: Tables, pq: PQ, enc: Encoded, ids, out=None):
+    """reconstructed float vectors of rows `ids`: out[q] = pq.reconstruct of row ids[q], the
+    codes never written to memory (pqh_fetch_vectors).  out: (count, >= m * dsub) float32,
+    rows out.stride(0) apart."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty((ids.numel(), pq.m * pq.dsub), dtype=torch.float32,
+                          device=enc.stream.device)
+    check(lib().pqh_fetch_vectors(ctx.ptr, tables.ptr, pq.ptr, *_index_args(enc), _ptr(ids),
+                                  ids.numel(), _ptr(out), out.stride(0)), "pqh_fetch_vectors")
     return out
 
 

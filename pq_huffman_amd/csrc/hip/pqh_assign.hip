@@ -1592,6 +1592,15 @@ struct pqh_pq {
     float* d_sqc = nullptr;
 };
 
+int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_cent) {
+    if (!pq || !pq->d_cent) return PQH_ERR_ARG;
+    *m = pq->m;
+    *k = pq->k;
+    *dsub = pq->dsub;
+    *d_cent = pq->d_cent;
+    return PQH_OK;
+}
+
 namespace {
 
 // A[row][slot] of one subspace for the pass layout of Plan<D> (-2 ch | -2 cl, both exact

@@ -4,6 +4,7 @@
 //   huffman_indices.bin    u64 N + stream (zero padded)
 //   huffman_stats.txt      JSON line appended (stats.c)
 // plus the decode sidecar huffman_chunks.bin (pqh extension, see pqh.h).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -277,6 +278,120 @@ extern "C" int pqh_decode_files(const char* in_prefix, unsigned char** codes_out
     PQH_HIP(ctx, hipMemcpy(out, d_codes.p, n * m * esz, hipMemcpyDeviceToHost));
     *codes_out = out;
     *n_out = (long long)n;
+    *m_out = (int)m;
+    return PQH_OK;
+}
+
+// Rows [first, first + count) of the files under in_prefix: the range's chunks are cut out of
+// the sidecar and the stream on the host (index entries j_lo ... j_hi, the bytes between the
+// first chunk's offset and the next chunk's after the last), rebased to a stream of their own
+// whose row 0 is row j_lo * C, and decoded by pqh_decode_range.  Every check of the files
+// comes before the first device call.
+extern "C" int pqh_decode_files_range(const char* in_prefix, long long first, long long count,
+                                      unsigned char** codes_out, int* m_out) {
+    if (!in_prefix || !codes_out || !m_out || first < 0 || count <= 0) return PQH_ERR_ARG;
+    *codes_out = nullptr;
+    FILE* cf = fopen(path_of(in_prefix, "huffman_codebooks.bin").c_str(), "rb");
+    if (!cf) return PQH_ERR_ARG;
+    uint32_t m = 0;
+    if (fread(&m, 4, 1, cf) != 1 || m == 0 || m > 16) {
+        fclose(cf);
+        return PQH_ERR_CORRUPT;
+    }
+    std::vector<huffman_codebook_t> cbs(m);
+    for (uint32_t i = 0; i < m; ++i) huffman_codebook_load(&cbs[i], cf);
+    fclose(cf);
+    const int context = cbs[0].is_context;
+    const int k = cbs[0].alphabet_size;
+    const size_t esz = k <= 256 ? 1 : 2;
+    FILE* ef = nullptr;
+    FILE* sf = nullptr;
+    auto fail = [&](int rc) {
+        for (auto& cb : cbs) huffman_codebook_destroy(&cb);
+        if (ef) fclose(ef);
+        if (sf) fclose(sf);
+        return rc;
+    };
+    ef = fopen(path_of(in_prefix, "huffman_indices.bin").c_str(), "rb");
+    unsigned long long n = 0;
+    if (!ef || fread(&n, 8, 1, ef) != 1) return fail(PQH_ERR_ARG);
+    fseek(ef, 0, SEEK_END);
+    const long long fsize = ftell(ef);
+    const unsigned long long bytes = fsize > 8 ? (unsigned long long)(fsize - 8) : 0;
+    if ((unsigned long long)first + (unsigned long long)count > n) return fail(PQH_ERR_ARG);
+
+    const std::string side = path_of(in_prefix, "huffman_chunks.bin");
+    auto no_index = [&](const char* why) {
+        fprintf(stderr, "pqh_decode_files_range: %s %s (a row range needs the chunk index)\n",
+                side.c_str(), why);
+        return fail(PQH_ERR_ARG);
+    };
+    sf = fopen(side.c_str(), "rb");
+    if (!sf) return no_index("is missing");
+    Sidecar h;
+    if (fread(&h, sizeof(h), 1, sf) != 1 || memcmp(h.magic, "PQHC", 4) || h.n != n || h.m != m ||
+        h.context != (uint32_t)context || h.chunk_vectors == 0 || h.raw_first != 1 ||
+        h.chunks != (n + h.chunk_vectors - 1) / h.chunk_vectors)
+        return no_index("does not belong to this stream");
+    const long long C = h.chunk_vectors;
+    const long long j_lo = first / C, j_hi = (first + count - 1) / C, nch = j_hi - j_lo + 1;
+    const bool has_next = (unsigned long long)(j_hi + 1) < h.chunks;
+    std::vector<unsigned long long> coff(nch + 1, bytes * 8);
+    std::vector<unsigned char> cprev((size_t)(nch + 1) * m * esz, 0);
+    const size_t want = (size_t)nch + (has_next ? 1 : 0);
+    bool ok = !fseek(sf, (long)(sizeof(h) + (size_t)j_lo * 8), SEEK_SET) &&
+              fread(coff.data(), 8, want, sf) == want;
+    if (ok && context)
+        ok = !fseek(sf, (long)(sizeof(h) + (size_t)h.chunks * 8 + (size_t)j_lo * m * esz), SEEK_SET) &&
+             fread(cprev.data(), m * esz, (size_t)nch, sf) == (size_t)nch;
+    if (!ok) return no_index("is truncated");
+    if (coff[0] > coff[nch] || coff[nch] > bytes * 8) return fail(PQH_ERR_CORRUPT);
+    // the bytes of these chunks, from the 32-bit word the first one starts in
+    const unsigned long long b0 = (coff[0] / 32) * 4;
+    const unsigned long long len = std::min(bytes, (coff[nch] + 7) / 8) - b0;
+    const unsigned long long sbytes = std::max<unsigned long long>(4, (len + 3) / 4 * 4);
+    std::vector<unsigned char> stream(sbytes + 8, 0);
+    if (fseek(ef, (long)(8 + b0), SEEK_SET) || (len && fread(stream.data(), 1, len, ef) != len))
+        return fail(PQH_ERR_CORRUPT);
+    for (auto& o : coff) o -= b0 * 8;
+    const long long n_sub = std::min<long long>((long long)n, (j_hi + 1) * C) - j_lo * C;
+
+    CtxGuard g;
+    int rc = pqh_ctx_create(&g.ctx, 0);
+    if (rc) return fail(rc);
+    pqh_ctx* ctx = g.ctx;
+    pqh_tables_t* tab = nullptr;
+    rc = pqh_tables_create(ctx, cbs.data(), (int)m, &tab);
+    fail(0);   // (the files and the host code books are done with)
+    ef = sf = nullptr;
+    cbs.clear();
+    if (rc) return rc;
+    DevBuf<unsigned char> d_stream, d_cprev, d_codes;
+    DevBuf<unsigned long long> d_coff;
+    if ((rc = d_stream.alloc(ctx, stream.size())) || (rc = d_coff.alloc(ctx, coff.size())) ||
+        (rc = d_cprev.alloc(ctx, cprev.size())) || (rc = d_codes.alloc(ctx, (size_t)count * m * esz))) {
+        pqh_tables_destroy(tab);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(d_stream.p, stream.data(), stream.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_coff.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_cprev.p, cprev.data(), cprev.size(), hipMemcpyHostToDevice, ctx->stream);
+    rc = e == hipSuccess ? pqh_decode_range(ctx, tab, d_stream.p, sbytes, n_sub, j_lo == 0 ? 1 : 0,
+                                            (int)C, d_coff.p, d_cprev.p, first - j_lo * C, count,
+                                            d_codes.p)
+                         : PQH_ERR_HIP;
+    if (!rc) rc = pqh_decode_status(ctx);
+    pqh_tables_destroy(tab);
+    if (rc) return rc;
+    unsigned char* out = (unsigned char*)malloc((size_t)count * m * esz + 1);
+    if (!out) return PQH_ERR_NOMEM;
+    if (hipMemcpy(out, d_codes.p, (size_t)count * m * esz, hipMemcpyDeviceToHost) != hipSuccess) {
+        free(out);
+        return PQH_ERR_HIP;
+    }
+    *codes_out = out;
     *m_out = (int)m;
     return PQH_OK;
 }

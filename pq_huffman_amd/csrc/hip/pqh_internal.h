@@ -79,6 +79,9 @@ int pqh_kmeans_update_launch(pqh_ctx* ctx, const long long* d_sums, const unsign
 // caller streaming chunks of a multiple of 256 rows gets pqh_pq_error's sum bit for bit)
 int pqh_pq_error_accum(pqh_ctx* ctx, const pqh_pq_t* pq, const float* d_x, long long n,
                        long long ld_x, const void* d_codes, double* sum);
+// a prepared codebook's shape and its device centroids [m][k][dsub] (pqh_assign.hip), for the
+// fused reconstruction of pqh_fetch_vectors; PQH_ERR_ARG for a null codebook
+int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_cent);
 // pqh_shard_encode's histogram / size / write with this shard's raw-first flag in device
 // memory (1: row 0 raw, no halo pair; 0: row 0 in the context of d_prev_row) -- pqh_huff.hip
 extern "C" {

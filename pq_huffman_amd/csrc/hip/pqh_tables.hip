@@ -14,6 +14,9 @@
 //               subtables for the prefixes of longer codes, ranges taken from a pool head.
 //  dec_chunks   huffman_decoder.c:211-255: one lane per chunk of C vectors; a symbol costs
 //               one table load instead of one trie step per bit (huffman_decode.c:137-191).
+//  sel_rows     the same decode for selected rows only: one lane per requested id, walking
+//  dec_range    its chunk from the chunk index; the cut chunks of a row range; optionally
+//               fused with the PQ reconstruction (pqh_decode_select / _range / pqh_fetch_vectors).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -2229,6 +2232,358 @@ dec_rows(const uint32_t* __restrict__ words, long long nwords, long long n, int 
     if (!ok) atomicOr(err, 1ull);
 }
 
+// ---- random access: selected rows, fused reconstruction, row ranges -------------------
+// (pqh_decode_select / pqh_fetch_vectors / pqh_decode_range).  The chunk index is the only
+// structure these need: a row is reached by walking its chunk from the chunk's bit offset,
+// in the chunk's stored context.  The ids of a wave are scattered over the stream, so there
+// is no window to stage: every lane reads the global stream through SelRd -- BitRd, based
+// at the word its chunk starts in (BitRd's 32-bit word indices then serve a stream of any
+// length) and clamped to the stream's last word.  A start past the stream is refused before
+// anything is read; the caller compares pos() with the stream's length after its walk.
+
+// BitRd whose skip loads the next word only when the buffer needs it: a load with 64
+// distinct lane addresses is what a step of these walks pays for, and only the lanes that
+// refill take part in it (dec_rows reads its window from LDS, where the branch-free refill
+// is the cheaper form)
+struct LazyRd : BitRd<false> {
+    __device__ __forceinline__ void skip(int nb) {   // nb <= 32
+        buf <<= nb;
+        have -= nb;
+        if (have <= 32) {
+            buf |= (unsigned long long)load(next) << (32 - have);
+            next += 1u;
+            have += 32;
+        }
+    }
+};
+
+struct SelRd {
+    LazyRd br;
+    unsigned long long base_bits;
+    __device__ __forceinline__ bool init(const uint32_t* words, long long nwords,
+                                         unsigned long long off) {
+        if (off > (unsigned long long)nwords * 32) return false;
+        const long long bw = min((long long)(off >> 5), nwords - 1);
+        br.w = words + bw;
+        br.lim = (uint32_t)min(nwords - 1 - bw, 0xFFFFFFF0ll);
+        base_bits = (unsigned long long)bw * 32;
+        br.init(off - base_bits);   // (at most bit 32 of the base word: the stream's end)
+        return true;
+    }
+    __device__ __forceinline__ unsigned long long pos() const {
+        return base_bits + (unsigned long long)br.next * 32 - (unsigned long long)br.have;
+    }
+};
+
+// ceil(log2 K): the raw bits per part of global row 0 (huffman_decode.c:73-76)
+__device__ __forceinline__ int warm_bits_of(int k) {
+    int wb = 1;
+    while ((1 << wb) < k) ++wb;
+    return wb;
+}
+
+// `steps` rows of one chunk, keeping only the running row: rows of NW u64 words as in
+// dec_row_lane (prev = the chunk's context row on entry, the last decoded row on return).
+template <bool CTX, int NW, int SB>
+__device__ __forceinline__ bool sel_walk_packed(LazyRd& br, const Row8Tabs& T, bool raw,
+                                                int steps, unsigned long long (&prev)[NW]) {
+    constexpr int PW = 64 / SB;
+    constexpr unsigned SMASK = (1u << SB) - 1u;
+    const unsigned roots = CTX ? (unsigned)T.k : 1u;
+    int s = 0;
+    if (CTX && raw) {
+        const int wb = warm_bits_of(T.k);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            prev[w] = 0;
+#pragma unroll 1
+            for (int i = 0; i < PW; ++i) {
+                prev[w] |= (unsigned long long)br.peek(wb) << (SB * i);
+                br.skip(wb);
+            }
+        }
+        s = 1;
+    }
+    for (; s < steps; ++s) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            unsigned long long row = 0;
+#pragma unroll 1
+            for (int i = 0; i < PW; ++i) {
+                const unsigned part = (unsigned)(w * PW + i);
+                const unsigned tab =
+                    part * roots + (CTX ? (unsigned)(prev[w] >> (SB * i)) & SMASK : 0u);
+                const int sym = dec_sym8(br, T, tab);
+                if (sym < 0) return false;
+                row |= (unsigned long long)sym << (SB * i);
+            }
+            prev[w] = row;
+        }
+    }
+    return true;
+}
+
+// the same walk for any m <= 16: a plain loop over the parts, the running row in the lane's
+// LDS slot (row = the chunk's context row on entry)
+template <bool CTX, typename CodeT>
+__device__ __forceinline__ bool sel_walk_parts(LazyRd& br, const Row8Tabs& T, int m, bool raw,
+                                               int steps, CodeT* row) {
+    const unsigned roots = CTX ? (unsigned)T.k : 1u;
+    int s = 0;
+    if (CTX && raw) {
+        const int wb = warm_bits_of(T.k);
+        for (int i = 0; i < m; ++i) {
+            row[i] = (CodeT)br.peek(wb);
+            br.skip(wb);
+        }
+        s = 1;
+    }
+    for (; s < steps; ++s) {
+#pragma unroll 1
+        for (int i = 0; i < m; ++i) {
+            const unsigned tab = (unsigned)i * roots + (CTX ? (unsigned)row[i] : 0u);
+            const int sym = dec_sym8(br, T, tab);
+            if (sym < 0) return false;
+            row[i] = (CodeT)sym;
+        }
+    }
+    return true;
+}
+
+// One lane per requested id v (huffman_decoder.c:211-255 for the rows asked for): chunk
+// j = v / C from chunk_off[j] in the context chunk_prev[j] (raw row 0 for j = 0 when
+// raw_first), rows j*C ... v, row v into output slot q.  NW > 0: rows of NW u64 words (8 or
+// 16 u8 codes, 8 u16 codes) in registers; NW = 0: any m <= 16, per part.  The wave's 64
+// result rows are staged in LDS and stored whole (FETCH = false), or reconstructed from
+// there (FETCH: x_hat[q] = concat_i cent[i][code_i], every float row written by the whole
+// wave as consecutive 16-byte stores; the codes never reach memory).  An id outside [0, n)
+// gives a zero row and error bit 2; an invalid code, a chunk offset or a symbol past the
+// stream a zero row and error bit 1.
+template <typename CodeT, int NW, bool CTX, bool FETCH>
+__global__ void __launch_bounds__(64)
+sel_rows(const uint32_t* __restrict__ words, long long nwords, long long n, int m, int raw_first,
+         int chunk_vectors, const unsigned long long* __restrict__ chunk_off,
+         const void* __restrict__ chunk_prev, Row8Tabs T, const long long* __restrict__ ids,
+         long long count, void* __restrict__ out, long long ld_out, const float* __restrict__ cent,
+         int dsub, unsigned long long* __restrict__ err) {
+    __shared__ __attribute__((aligned(16))) unsigned char stage_b[64 * 16 * sizeof(CodeT)];
+    __shared__ unsigned char dead[64];
+    CodeT* stage = reinterpret_cast<CodeT*>(stage_b);
+    const int lane = threadIdx.x;
+    const long long q0 = (long long)blockIdx.x * 64;
+    const int rows = (int)min(64ll, count - q0);
+    CodeT* row = stage + lane * m;
+    unsigned flag = 0;
+    bool good = false;
+    if (lane < rows) {
+        const long long v = ids[q0 + lane];
+        if (v < 0 || v >= n) {
+            flag = 2;
+        } else {
+            const long long j = v / chunk_vectors;
+            const int steps = (int)(v - j * chunk_vectors) + 1;
+            const bool raw = CTX && j == 0 && raw_first;
+            SelRd rd;
+            good = rd.init(words, nwords, chunk_off[j]);
+            if (good) {
+                if constexpr (NW > 0) {
+                    unsigned long long prev[NW];
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)
+                        prev[w] = (CTX && !raw)
+                                      ? static_cast<const unsigned long long*>(chunk_prev)[j * NW + w]
+                                      : 0ull;
+                    good = sel_walk_packed<CTX, NW, 8 * (int)sizeof(CodeT)>(rd.br, T, raw, steps, prev);
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) reinterpret_cast<unsigned long long*>(row)[w] = prev[w];
+                } else {
+                    for (int i = 0; i < m; ++i)
+                        row[i] = (CTX && !raw) ? static_cast<const CodeT*>(chunk_prev)[j * m + i]
+                                               : (CodeT)0;
+                    good = sel_walk_parts<CTX, CodeT>(rd.br, T, m, raw, steps, row);
+                }
+                good = good && rd.pos() <= (unsigned long long)nwords * 32;
+            }
+            if (!good) flag = 1;
+        }
+    }
+    if (!good)
+        for (int i = 0; i < m; ++i) row[i] = (CodeT)0;
+    dead[lane] = good ? 0 : 1;
+    if (flag) atomicOr(err, (unsigned long long)flag);
+    lds_barrier();
+    if constexpr (!FETCH) {
+        // the workgroup's rows are contiguous in the output: whole-row stores
+        const long long nbytes = (long long)rows * m * (long long)sizeof(CodeT);
+        unsigned char* dst = static_cast<unsigned char*>(out) + q0 * m * (long long)sizeof(CodeT);
+        long long done = 0;
+        if (!(reinterpret_cast<uintptr_t>(dst) & 3u)) {
+            done = nbytes & ~3ll;
+            for (long long q = lane; q < done / 4; q += 64)
+                reinterpret_cast<uint32_t*>(dst)[q] = reinterpret_cast<const uint32_t*>(stage_b)[q];
+        }
+        for (long long q = done + lane; q < nbytes; q += 64) dst[q] = stage_b[q];
+    } else {
+        float* o = static_cast<float*>(out) + q0 * ld_out;
+        const int d = m * dsub;
+        const long long k = T.k;
+        if (!(d & 3) && !(ld_out & 3) && !(reinterpret_cast<uintptr_t>(out) & 15u)) {
+            const int per = d >> 2;   // 16-byte pieces of a row; a piece may span two parts
+            for (int it = lane; it < rows * per; it += 64) {
+                const int r = it / per, c = (it - r * per) * 4;
+                const CodeT* cr = stage + r * m;
+                float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!dead[r]) {
+                    if (!(dsub & 3)) {
+                        const int i = c / dsub;
+                        val = *reinterpret_cast<const float4*>(cent + (i * k + cr[i]) * dsub + (c - i * dsub));
+                    } else {
+                        float e[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int i = (c + u) / dsub;
+                            e[u] = cent[(i * k + cr[i]) * dsub + (c + u - i * dsub)];
+                        }
+                        val = make_float4(e[0], e[1], e[2], e[3]);
+                    }
+                }
+                *reinterpret_cast<float4*>(o + (long long)r * ld_out + c) = val;
+            }
+        } else {
+            for (int it = lane; it < rows * d; it += 64) {
+                const int r = it / d, c = it - r * d;
+                const int i = c / dsub;
+                o[(long long)r * ld_out + c] =
+                    dead[r] ? 0.f : cent[(i * k + stage[r * m + i]) * dsub + (c - i * dsub)];
+            }
+        }
+    }
+}
+
+// Rows [first, first + count) where they are not whole chunks: one lane per chunk, as
+// dec_rows, walking its chunk from the start and storing only the rows inside the range
+// (the first and the last chunk of a range may be cut; the whole chunks between them go
+// through pqh_decode's kernels, skipped here as [skip_at, skip_at + skip_len)).  The running
+// row is the lane's LDS slot; a failed chunk's rows of the range are zeroed.
+template <typename CodeT, bool CTX>
+__global__ void __launch_bounds__(64)
+dec_range(const uint32_t* __restrict__ words, long long nwords, long long n, int m, int raw_first,
+          int chunk_vectors, const unsigned long long* __restrict__ chunk_off,
+          const CodeT* __restrict__ chunk_prev, Row8Tabs T, long long first, long long count,
+          long long jbeg, long long skip_at, long long skip_len, long long lanes,
+          CodeT* __restrict__ out, unsigned long long* __restrict__ err) {
+    __shared__ CodeT stage[64 * 16];
+    const long long idx = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (idx >= lanes) return;   // (no barriers below: lanes are independent)
+    long long j = jbeg + idx;
+    if (j >= skip_at) j += skip_len;
+    const long long v0 = j * chunk_vectors;
+    const long long lo = max(v0, first);
+    const long long hi = min(min(n, v0 + chunk_vectors), first + count);
+    if (lo >= hi) return;
+    CodeT* row = stage + threadIdx.x * m;
+    const bool raw = CTX && j == 0 && raw_first;
+    for (int i = 0; i < m; ++i) row[i] = (CTX && !raw) ? chunk_prev[j * m + i] : (CodeT)0;
+    const unsigned roots = CTX ? (unsigned)T.k : 1u;
+    const int wb = warm_bits_of(T.k);
+    SelRd rd;
+    bool ok = rd.init(words, nwords, chunk_off[j]);
+    for (long long v = v0; v < hi && ok; ++v) {
+#pragma unroll 1
+        for (int i = 0; i < m; ++i) {
+            int sym;
+            if (raw && v == v0) {
+                sym = (int)rd.br.peek(wb);
+                rd.br.skip(wb);
+            } else {
+                sym = dec_sym8(rd.br, T, (unsigned)i * roots + (CTX ? (unsigned)row[i] : 0u));
+            }
+            if (sym < 0) {
+                ok = false;
+                break;
+            }
+            row[i] = (CodeT)sym;
+        }
+        if (ok && v >= lo)
+            for (int i = 0; i < m; ++i) out[(v - first) * m + i] = row[i];
+    }
+    if (ok && rd.pos() > (unsigned long long)nwords * 32) ok = false;
+    if (!ok) {
+        for (long long q = (lo - first) * m; q < (hi - first) * m; ++q) out[q] = (CodeT)0;
+        atomicOr(err, 1ull);
+    }
+}
+
+// the chunk offsets handed to pqh_decode's kernels by pqh_decode_range: within the stream
+// and not decreasing, else the decode error (those kernels clamp their reads but report only
+// invalid codes)
+__global__ void __launch_bounds__(256)
+chk_offsets(const unsigned long long* __restrict__ off, long long cnt, int last_has_next,
+            unsigned long long total_bits, unsigned long long* __restrict__ err) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= cnt) return;
+    const unsigned long long a = off[j];
+    const bool next = j + 1 < cnt || last_has_next;
+    if (a > total_bits || (next && a > off[j + 1])) atomicOr(err, 1ull);
+}
+
+// argument checks shared by the random-access calls
+int sel_check(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+              unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
+              const unsigned long long* d_chunk_offsets, const void* d_chunk_prev, long long count,
+              const void* d_out) {
+    if (!ctx || !t || n < 0 || chunk_vectors <= 0 || count < 0) return PQH_ERR_ARG;
+    if (count > 0 && (!d_out || (n > 0 && (!d_stream || !d_chunk_offsets || stream_bytes < 4))))
+        return PQH_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
+    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
+    if (t->m > 16 || (t->context && t->k > 256)) return PQH_ERR_UNSUPPORTED;
+    return pqh_use_device(ctx);
+}
+
+Row8Tabs sel_tabs(const pqh_tables_t* t) {
+    return Row8Tabs{t->d_lut1, t->d_lut2, t->d_meta, t->d_long, t->d_long_cnt, t->lut2_cap,
+                    t->l1_bits, t->k, 0};
+}
+
+// sel_rows over `count` ids: codes [count][m] (FETCH = false) or float rows ld_out apart
+template <bool FETCH>
+int sel_launch(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+               unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
+               const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
+               const long long* d_ids, long long count, void* d_out, long long ld_out,
+               const float* d_cent, int dsub) {
+    const int esz = t->k <= 256 ? 1 : 2;
+    const int row_bytes = t->m * esz;
+    // rows of whole u64 words in registers (the shapes of dec_rows), else the per-part walk
+    const bool packed = (row_bytes == 8 || row_bytes == 16) && (esz == 1 || t->m == 8) &&
+                        !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
+    const int nw_row = packed ? row_bytes / 8 : 0;
+    const Row8Tabs T = sel_tabs(t);
+    const uint32_t* wp = reinterpret_cast<const uint32_t*>(d_stream);
+    const long long nwords = (long long)(stream_bytes / 4);
+    const unsigned blocks = (unsigned)((count + 63) / 64);
+#define PQH_SEL(CT, NW, CTX)                                                                     \
+    hipLaunchKernelGGL((sel_rows<CT, NW, CTX, FETCH>), dim3(blocks), dim3(64), 0, ctx->stream,   \
+                       wp, nwords, n, t->m, raw_first, chunk_vectors, d_chunk_offsets,           \
+                       d_chunk_prev, T, d_ids, count, d_out, ld_out, d_cent, dsub,               \
+                       ctx->d_diag + 1)
+    if (esz == 2) {
+        if (nw_row) PQH_SEL(uint16_t, 2, false); else PQH_SEL(uint16_t, 0, false);
+    } else if (t->context) {
+        if (nw_row == 1) PQH_SEL(uint8_t, 1, true);
+        else if (nw_row == 2) PQH_SEL(uint8_t, 2, true);
+        else PQH_SEL(uint8_t, 0, true);
+    } else {
+        if (nw_row == 1) PQH_SEL(uint8_t, 1, false);
+        else if (nw_row == 2) PQH_SEL(uint8_t, 2, false);
+        else PQH_SEL(uint8_t, 0, false);
+    }
+#undef PQH_SEL
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
 // diagnostics only (pqh_debug_poison_lds): fills a whole CU's LDS (160 KB) with `value`, so a
 // kernel launched after it on any CU finds that pattern, not zeros or an earlier kernel's
 // data, in whatever LDS it reads before writing -- a test for stale-LDS reads
@@ -2717,7 +3072,101 @@ int pqh_decode_status(pqh_ctx_t* ctx) {
     PQH_HIP(ctx, hipMemcpyAsync(&e, ctx->d_diag + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     PQH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (e) PQH_HIP(ctx, hipMemsetAsync(ctx->d_diag + 1, 0, 8, ctx->stream));   // (sticky until read)
-    return e ? pqh_set_error(ctx, PQH_ERR_CORRUPT, "invalid code in stream") : PQH_OK;
+    // bit 0: an invalid code (every decoder); bit 1: an id outside the rows (pqh_decode_select,
+    // pqh_fetch_vectors) -- reported only when no code was invalid
+    if (e & 1ull) return pqh_set_error(ctx, PQH_ERR_CORRUPT, "invalid code in stream");
+    return e ? pqh_set_error(ctx, PQH_ERR_ARG, "row id outside the stream's rows") : PQH_OK;
+}
+
+int pqh_decode_select(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                      unsigned long long stream_bytes, long long n, int raw_first,
+                      int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                      const void* d_chunk_prev, const long long* d_ids, long long count,
+                      void* d_codes) {
+    int rc = sel_check(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                       d_chunk_offsets, d_chunk_prev, count, d_codes);
+    if (rc) return rc;
+    if (count == 0) return PQH_OK;
+    if (!d_ids) return PQH_ERR_ARG;
+    return sel_launch<false>(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                             d_chunk_offsets, d_chunk_prev, d_ids, count, d_codes, 0, nullptr, 0);
+}
+
+int pqh_fetch_vectors(pqh_ctx_t* ctx, const pqh_tables_t* t, const pqh_pq_t* pq,
+                      const unsigned char* d_stream, unsigned long long stream_bytes, long long n,
+                      int raw_first, int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                      const void* d_chunk_prev, const long long* d_ids, long long count,
+                      float* d_out, long long ld_out) {
+    int m = 0, k = 0, dsub = 0;
+    const float* d_cent = nullptr;
+    if (!t || pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || m != t->m || k != t->k ||
+        ld_out < (long long)m * dsub)
+        return PQH_ERR_ARG;
+    int rc = sel_check(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                       d_chunk_offsets, d_chunk_prev, count, d_out);
+    if (rc) return rc;
+    if (count == 0) return PQH_OK;
+    if (!d_ids || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return PQH_ERR_ARG;
+    return sel_launch<true>(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                            d_chunk_offsets, d_chunk_prev, d_ids, count, d_out, ld_out, d_cent,
+                            dsub);
+}
+
+int pqh_decode_range(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                     unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
+                     const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
+                     long long first, long long count, void* d_codes) {
+    int rc = sel_check(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                       d_chunk_offsets, d_chunk_prev, count, d_codes);
+    if (rc) return rc;
+    if (first < 0 || first > n - count) return PQH_ERR_ARG;
+    if (count == 0) return PQH_OK;
+    const long long C = chunk_vectors;
+    const int esz = t->k <= 256 ? 1 : 2;
+    if (reinterpret_cast<uintptr_t>(d_codes) & (uintptr_t)(esz - 1)) return PQH_ERR_ARG;
+    const long long chunks = (n + C - 1) / C;
+    const long long end = first + count;
+    const long long j_lo = first / C, j_hi = (end - 1) / C;
+    // the whole chunks [ja, jb) of the range go through pqh_decode (its windowed kernels, with
+    // the index pointers moved to chunk ja); the cut chunks at either end -- and every chunk
+    // when that output would not be 4-byte aligned -- through dec_range
+    long long ja = j_lo + (first % C ? 1 : 0);
+    long long jb = j_hi + 1 - ((end % C && end != n) ? 1 : 0);
+    unsigned char* o_in = static_cast<unsigned char*>(d_codes) + (ja * C - first) * t->m * esz;
+    if (jb <= ja || (reinterpret_cast<uintptr_t>(o_in) & 3u)) jb = ja = j_hi + 1;
+    if (jb > ja) {
+        const unsigned char* cp = static_cast<const unsigned char*>(d_chunk_prev);
+        rc = pqh_decode(ctx, t, d_stream, stream_bytes, std::min(n, jb * C) - ja * C,
+                        ja == 0 ? raw_first : 0, chunk_vectors, d_chunk_offsets + ja,
+                        cp ? cp + ja * t->m * esz : nullptr, o_in);
+        if (rc == PQH_ERR_UNSUPPORTED) {   // (a chunk too long for its staging)
+            jb = ja = j_hi + 1;
+        } else if (rc) {
+            return rc;
+        } else {
+            const long long cnt = jb - ja;
+            hipLaunchKernelGGL(chk_offsets, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0,
+                               ctx->stream, d_chunk_offsets + ja, cnt, jb < chunks ? 1 : 0,
+                               (stream_bytes / 4) * 32ull, ctx->d_diag + 1);
+        }
+    }
+    const long long lanes = (j_hi - j_lo + 1) - (jb - ja);
+    if (lanes > 0) {
+        const Row8Tabs T = sel_tabs(t);
+        const unsigned blocks = (unsigned)((lanes + 63) / 64);
+#define PQH_RANGE(CT, CTX)                                                                       \
+    hipLaunchKernelGGL((dec_range<CT, CTX>), dim3(blocks), dim3(64), 0, ctx->stream,             \
+                       reinterpret_cast<const uint32_t*>(d_stream), (long long)(stream_bytes / 4), \
+                       n, t->m, raw_first, chunk_vectors, d_chunk_offsets,                       \
+                       static_cast<const CT*>(d_chunk_prev), T, first, count, j_lo, ja, jb - ja, \
+                       lanes, static_cast<CT*>(d_codes), ctx->d_diag + 1)
+        if (esz == 2) PQH_RANGE(uint16_t, false);
+        else if (t->context) PQH_RANGE(uint8_t, true);
+        else PQH_RANGE(uint8_t, false);
+#undef PQH_RANGE
+    }
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
 }
 
 // Chunk index of a stream that came without a sidecar: a sequential walk over a HOST copy
