@@ -61,6 +61,29 @@ namespace {
 #ifndef PQH_ASSIGN_RQ
 #define PQH_ASSIGN_RQ 128
 #endif
+// The deferred re-rank batch (rerank32) and the kernel's start and end phases; 0 builds the
+// earlier form of each, for A/B runs from one tree (EXPERIMENTS.md §9):
+#ifndef PQH_ASSIGN_RRMASK   // candidate mask: a compare + an add-with-carry per score
+#define PQH_ASSIGN_RRMASK 1
+#endif
+#ifndef PQH_ASSIGN_RRPAIR   // re-screen two tiles per iteration (both MFMA chains first)
+#define PQH_ASSIGN_RRPAIR 1
+#endif
+#ifndef PQH_ASSIGN_RRPACK   // the batch's B operands by the main loop's packed conversions
+#define PQH_ASSIGN_RRPACK 1
+#endif
+#ifndef PQH_ASSIGN_RRPICK   // a lane's next candidate by selects and one bit scan
+#define PQH_ASSIGN_RRPICK 1
+#endif
+#ifndef PQH_ASSIGN_RRSKIP   // a candidate slot that no lane fills is not evaluated
+#define PQH_ASSIGN_RRSKIP 1
+#endif
+#ifndef PQH_ASSIGN_HANDOVER   // the first finisher of a wave pair leaves its queue to the second
+#define PQH_ASSIGN_HANDOVER 1
+#endif
+#ifndef PQH_ASSIGN_EARLYX   // first ticket and first x prefetch before the LDS fill
+#define PQH_ASSIGN_EARLYX 1
+#endif
 constexpr int kRqLds = PQH_ASSIGN_RQ;   // deferred re-rank queue entries per wave (LDS)
 constexpr int kWavesPerWG = PQH_ASSIGN_WPG;   // subspace waves per workgroup
 constexpr int kNB = PQH_ASSIGN_NB;            // 32-vector blocks screened together per step
@@ -551,6 +574,26 @@ __device__ __forceinline__ int tile_row(int t, int i, int h) {
     return 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
 }
 
+// (bits << 16) | the tile's candidate mask: bit i set iff acc[i] <= thr (never for a NaN).
+// RRMASK: 2 VALU per score -- the compare writes its lane mask to a scalar register pair (a
+// compiler-generated read of the MFMA result, so it gets its wait states) and an add-with-carry
+// bits + bits + carry shifts the lane's bit in; register 15 goes first and ends in bit 15.
+__device__ __forceinline__ uint32_t score_mask(const f32x16& acc, float thr, uint32_t bits) {
+#if PQH_ASSIGN_RRMASK && defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int i = 15; i >= 0; --i) {
+        const unsigned long long le = __ballot(acc[i] <= thr);
+        asm("v_addc_co_u32_e64 %0, vcc, %0, %0, %1" : "+v"(bits) : "s"(le) : "vcc");
+    }
+    return bits;
+#else
+    uint32_t mk = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mk |= (acc[i] <= thr ? 1u : 0u) << i;
+    return (bits << 16) | mk;
+#endif
+}
+
 // KT = centroid tiles of 32 (8: K = 256, A fragments in LDS; 128: K = 4096, A fragments
 // streamed from L2 a few tiles ahead, no fused histogram)
 // (dsub 32 and K = 4096 hold more live state per wave: two waves per SIMD, no spills)
@@ -584,6 +627,10 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
     // each wave's re-rank queue (the LDS budget stays at 32 KB, so a workgroup still fits on
     // a CU beside a code-table build's 112 KB)
     __shared__ uint2 rqs[kWavesPerWG][kRqLds];
+    // (HANDOVER) one mailbox per wave pair (w, w ^ 1): 0, or the first finisher's leftover
+    // count with bit 31 set (see the tail)
+    constexpr int kPairs = PQH_ASSIGN_HANDOVER && kWavesPerWG % 2 == 0 ? kWavesPerWG / 2 : 0;
+    __shared__ uint32_t rq_box[kPairs ? kPairs : 1];
 #ifndef PQH_ASSIGN_XLDS
 #define PQH_ASSIGN_XLDS 1
 #endif
@@ -630,18 +677,36 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
         if (lane == 0)
             __hip_atomic_store(rerank_next, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    {
+    // (EARLYX: the fill runs after the wave's first ticket request and first x prefetch are in
+    // flight, see below -- it writes neither xst nor the queue heads; the streamed K = 4096
+    // forms read Cn and the ring before that point and keep the fill here)
+    constexpr bool kEarlyX = PQH_ASSIGN_EARLYX != 0 && !kShareA;
+    auto fill_lds = [&]() {
         const uint4* src = reinterpret_cast<const uint4*>(afrag) + (long long)m * P::PA * KT * 64;
-        if constexpr (kLdsA)
-            for (int i = threadIdx.x; i < P::PA * KT * 64; i += blockDim.x) As[i] = src[i];
-        for (int i = threadIdx.x; i < KT * 2 * 16; i += blockDim.x)
-            Cn[i] = cnorm[(long long)m * KT * 2 * 16 + i];
+        constexpr int kNA = P::PA * KT * 64, kThreads = 64 * kWavesPerWG;
+        if constexpr (kLdsA && kEarlyX && kNA % kThreads == 0 && KT * 2 * 16 <= kThreads) {
+            // all of the thread's pieces requested before the first is stored: one round
+            // trip (a loop strided by blockDim.x waits for each piece in turn)
+            // (global reads and LDS writes cannot alias: the unrolled loads are clustered)
+            const int tid = (int)threadIdx.x;
+            if (KT * 2 * 16 == kThreads || tid < KT * 2 * 16)
+                Cn[tid] = cnorm[(long long)m * KT * 2 * 16 + tid];
+#pragma unroll
+            for (int j = 0; j < kNA / kThreads; ++j) As[tid + j * kThreads] = src[tid + j * kThreads];
+        } else {
+            if constexpr (kLdsA)
+                for (int i = threadIdx.x; i < kNA; i += blockDim.x) As[i] = src[i];
+            for (int i = threadIdx.x; i < KT * 2 * 16; i += blockDim.x)
+                Cn[i] = cnorm[(long long)m * KT * 2 * 16 + i];
+        }
         if (kLdsA && counts)
             for (int i = lane; i < K; i += 64) hist(wave)[i] = 0;
         if constexpr (kLdsA && kCentLds)
             for (int i = threadIdx.x; i < K * D; i += blockDim.x) Cf[i] = cent[(long long)m * K * D + i];
+        if ((int)threadIdx.x < kPairs) rq_box[threadIdx.x] = 0u;
         __syncthreads();   // the only workgroup barrier
-    }
+    };
+    if constexpr (!kEarlyX) fill_lds();
     // where the A fragments come from: the LDS copy, or this subspace's slice in global
     const uint4* const asrc =
         kLdsA ? As : reinterpret_cast<const uint4*>(afrag) + (long long)m * P::PA * KT * 64;
@@ -781,8 +846,10 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
         }
     };
     // Deferred re-rank: a vector whose screening gap is too small is appended to this wave's
-    // LDS queue and finished after the wave's last chunk (tail_rerank); only when the queue
-    // is full, or x is not finite, does the wave re-rank inline.
+    // LDS queue and finished 32 at a time (rerank32): right after the step that fills a batch,
+    // and after the wave's last chunk for what is left -- by this wave or, handed over through
+    // the pair's mailbox, by its partner (see the tail).  Only when the queue is full, or x is
+    // not finite, does the wave re-rank inline.
     unsigned qn = 0;
 
     // One step = a chunk of kNB consecutive 32-vector blocks, screened together: each tile's
@@ -1259,6 +1326,20 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
 #pragma unroll
         for (int j = 0; j < XD; ++j)   // (static indices: a dynamic one puts xv in scratch)
             xs[j] = valid ? (h ? xv[Slice<D>::dim(j, 1)] : xv[Slice<D>::dim(j, 0)]) : 0.0f;
+        bf16x8 Bm[P::PM];
+        bf16x8 Bl[P::PL];
+#if PQH_ASSIGN_RRPACK
+        // the main loop's own operand code (packed conversions; the same bf16 values as
+        // split_x + build_b, see make_b), and its remainder test
+        const bool lo = has_lo<D>(xs);
+#ifdef PQH_ASSIGN_STAMPS
+        unsigned long long rr1, rr2, rr3;
+        asm volatile("" ::"v"(xs[0]));
+        PQH_RR_STAMP(rr1);
+        rr_x += rr1 - rr0;
+#endif
+        make_b<D, true>(xs, h, Bm, Bl);
+#else
         float X;
         bool lo;
         float xh[XD], xl[XD];
@@ -1269,9 +1350,8 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
         PQH_RR_STAMP(rr1);
         rr_x += rr1 - rr0;
 #endif
-        bf16x8 Bm[P::PM];
-        bf16x8 Bl[P::PL];
         build_b<D>(xh, xl, h, Bm, Bl);
+#endif
         const bool lo_pass = __any(lo);
         float best = INFINITY;
         int bidx = 0x7FFFFFFF;
@@ -1286,16 +1366,31 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
             uint32_t cw[(kGT + 1) / 2];   // tiles t0 + 2w (bits 0-15) and t0 + 2w + 1 (16-31)
 #pragma unroll
             for (int w = 0; w < (kGT + 1) / 2; ++w) cw[w] = 0u;
+#if PQH_ASSIGN_RRPAIR
+            // Rolled over tile pairs (the tail keeps its registers few): both tiles' MFMA
+            // chains are issued before the first tile's compares, so the second chain runs
+            // under them.  The scores are tile_scores' own, whatever the order of the chains.
+            static_assert(kGT % 2 == 0, "tile pairs");
+#pragma unroll 1
+            for (int u = 0; u < kGT; u += 2) {
+                const f32x16 acc0 = tile_scores<D, KT>(asrc, Cn, lane, t0 + u, Bm, Bl, lo_pass);
+                const f32x16 acc1 = tile_scores<D, KT>(asrc, Cn, lane, t0 + u + 1, Bm, Bl, lo_pass);
+                uint32_t bits = score_mask(acc1, thr, 0u);   // tile t0 + u + 1: bits 16-31
+                bits = score_mask(acc0, thr, bits);          // tile t0 + u: bits 0-15
+                bits = valid ? bits : 0u;
+#pragma unroll
+                for (int w = 0; w < kGT / 2; ++w) cw[w] = w == (u >> 1) ? bits : cw[w];
+            }
+#else
 #pragma unroll 1
             for (int u = 0; u < kGT; ++u) {   // (rolled: the tail keeps its registers few)
                 const f32x16 acc = tile_scores<D, KT>(asrc, Cn, lane, t0 + u, Bm, Bl, lo_pass);
-                uint32_t bits = 0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) bits |= (acc[i] <= thr ? 1u : 0u) << i;
+                uint32_t bits = score_mask(acc, thr, 0u);
                 bits = (valid ? bits : 0u) << (16 * (u & 1));
 #pragma unroll
                 for (int w = 0; w < (kGT + 1) / 2; ++w) cw[w] |= w == (u >> 1) ? bits : 0u;
             }
+#endif
 #ifdef PQH_ASSIGN_STAMPS
             asm volatile("" ::"v"(cw[0]));
             PQH_RR_STAMP(rr2);
@@ -1304,10 +1399,46 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
             for (;;) {
                 int kc[kCand];
                 bool hc[kCand];
+                // (RRSKIP) use[c]: some lane of the wave has a candidate in slot c.  A lane fills
+                // its slots in order, so once no lane has a candidate bit left the remaining
+                // slots are neither extracted, loaded nor evaluated (most rounds hold one or two
+                // candidates per lane).  The slots that are evaluated keep their order.
+                bool use[kCand];
 #pragma unroll
                 for (int c = 0; c < kCand; ++c) {   // the lane's next candidate, if any
                     hc[c] = false;
                     kc[c] = 0;
+                    use[c] = true;
+                    if (PQH_ASSIGN_RRSKIP) {   // (tested on the masks: no extraction for nothing)
+                        uint32_t left = 0u;
+#pragma unroll
+                        for (int w = 0; w < (kGT + 1) / 2; ++w) left |= cw[w];
+                        use[c] = (c == 0 || use[c - 1]) && __any(left != 0u);
+                        if (!use[c]) continue;
+                    }
+#if PQH_ASSIGN_RRPICK
+                    // the first non-empty word by selects (its lane masks combine on the
+                    // scalar unit), one bit scan, and the row from the bit's position p in
+                    // the lane's mask of 16 kGT bits: tile p >> 4, register p & 15
+                    constexpr int NW = (kGT + 1) / 2;
+                    bool ne[NW], before = false;
+                    uint32_t sel = 0u, pbase = 0u;
+#pragma unroll
+                    for (int w = NW - 1; w >= 0; --w) {
+                        ne[w] = cw[w] != 0u;
+                        sel = ne[w] ? cw[w] : sel;
+                        pbase = ne[w] ? 32u * w : pbase;
+                    }
+                    const uint32_t rest = sel & (sel - 1u);
+                    const uint32_t p = pbase + (uint32_t)(__ffs((int)sel) - 1);
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        cw[w] = ne[w] && !before ? rest : cw[w];
+                        before |= ne[w];
+                    }
+                    hc[c] = before;
+                    kc[c] = before ? tile_row(t0 + (int)(p >> 4), (int)(p & 15u), h) : 0;
+#else
 #pragma unroll
                     for (int w = 0; w < (kGT + 1) / 2; ++w) {
                         if (!hc[c] && cw[w]) {
@@ -1317,14 +1448,17 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
                             kc[c] = tile_row(t0 + 2 * w + (i >> 4), i & 15, h);
                         }
                     }
+#endif
+                    if (!PQH_ASSIGN_RRSKIP && c == 0) use[c] = __any(hc[c]);
                 }
-                if (!__any(hc[0])) break;
+                if (!use[0]) break;
 #ifdef PQH_ASSIGN_STAMPS
                 ++rr_rounds;
 #endif
                 float cr[kCand][D];   // (lanes without a candidate read row 0)
 #pragma unroll
                 for (int c = 0; c < kCand; ++c) {
+                    if (!use[c]) continue;   // (wave-uniform)
                     const float* cp = cl + kc[c] * D;
                     if constexpr (D % 4 == 0) {
 #pragma unroll
@@ -1339,6 +1473,7 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
                 }
 #pragma unroll
                 for (int c = 0; c < kCand; ++c) {
+                    if (!use[c]) continue;
                     const float dd = exact_dist<D>(xv, cr[c]);
                     const int k = kc[c];
                     if (hc[c] && (dd < best || (dd == best && k < bidx))) { best = dd; bidx = k; }
@@ -1409,6 +1544,10 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
         else
             load_x(ch * kNB + b, xn[b]);
     }
+    // (EARLYX) the first ticket and the first chunk's x are in flight: their HBM round trips
+    // run under the fill's.  The barrier's wait covers the x DMA, so the first read_x_lds
+    // below sees its slices as before.
+    if constexpr (kEarlyX) fill_lds();
     while (ch < nchunk) {
         float xa[kNB][XD];
         if constexpr (kXLds) {
@@ -1458,12 +1597,43 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
     // same scores: same norms, and a lo pass adds exact zeros for bf16-exact x), the centroids
     // screening at or below thr are collected per lane, and only those few are evaluated in
     // exact fp32 direct form (first index among equal distances) -- instead of all K.
-    // Full batches were finished in the chunk loop (while the SIMD had other waves to run);
-    // the wave's last, partial batch runs here, without waiting for the workgroup's other waves.
+    // Full batches were finished in the chunk loop (while the SIMD had other waves to run).
+    // What is left (fewer than 32 entries per wave) runs here: with HANDOVER the first
+    // finisher of a wave pair leaves its entries to the second, so a pair runs one or two
+    // fuller batches instead of two partial ones; without it every wave runs its own.  No
+    // wave waits for another either way.  rerank32's cheaper forms (RRMASK, RRPAIR, RRPACK,
+    // RRPICK, RRSKIP) change which instructions build the candidate masks and which slots are
+    // evaluated, never a score or a distance: the scores are tile_scores' (the B operands are
+    // the main loop's own make_b), and a candidate set is evaluated as a whole.
 #ifdef PQH_ASSIGN_TAILPRIO   // (experiment) the re-rank tail ahead of other waves' main loops
     __builtin_amdgcn_s_setprio(PQH_ASSIGN_TAILPRIO);
 #endif
-    if (qn) {   // (qn < 32 here)
+    // (qn < 32 here)
+    if constexpr (kPairs > 0) {
+        // One exchange on the pair's mailbox decides: the wave that finds it empty has left
+        // its count there and exits -- its entries stay in its queue for the partner; the
+        // wave that finds a count runs the partner's entries with its own.  Each mailbox has
+        // two visitors, so the second one's word is never read, nobody waits, and every entry
+        // runs once whichever wave comes first.  (The queue entries were written by the same
+        // wave's earlier LDS stores; the release orders them before the exchange.)
+        uint32_t got = 0u;
+        if (lane == 0)
+            got = __hip_atomic_exchange(&rq_box[wave >> 1], 0x80000000u | qn, __ATOMIC_ACQ_REL,
+                                        __HIP_MEMORY_SCOPE_WORKGROUP);
+        got = __builtin_amdgcn_readfirstlane(got);
+        const unsigned pn = got & 0x7FFFFFFFu;
+        if (got != 0u) {
+            const unsigned tot = qn + pn;   // (< 64: at most two batches)
+#pragma unroll 1
+            for (unsigned e0 = 0; e0 < tot; e0 += 32u) {
+                const unsigned e = e0 + (unsigned)r;
+                const bool valid = e < tot;
+                const uint2 ent = !valid ? make_uint2(0u, 0u)
+                                  : e < qn ? rqs[wave][e] : rqs[wave ^ 1][e - qn];
+                rerank32(ent, valid);
+            }
+        }
+    } else if (qn) {
         const bool valid = (unsigned)r < qn;
         rerank32(valid ? rqs[wave][r] : make_uint2(0u, 0u), valid);
     }
