@@ -7,7 +7,7 @@
 //  enc_write               encode_*_data (huffman_encoder.c:207-238): each block scans its
 //                          per-vector lengths in LDS, ORs its codes into an LDS image of
 //                          its bit range, stores interior words and ORs its two edge words
-// (code tables and decode: pqh_tables.hip)
+// (code tables: pqh_tables.hip; decode: pqh_decode.hip)
 // Stream words are assembled MSB-first in 32-bit registers and byte-swapped on store, so
 // memory holds exactly the bytes bitstream.c writes.
 #include <algorithm>
@@ -21,7 +21,6 @@
 namespace {
 
 constexpr int kEncBlock = 512;   // vectors per encode workgroup (one thread each)
-constexpr int kMaxCodeLen = 56;
 constexpr int kHistChunk = 61440; // vectors per context-histogram workgroup (< 65536)
 
 template <typename CodeT>

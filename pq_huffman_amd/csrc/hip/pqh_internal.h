@@ -165,7 +165,8 @@ bool pqh_debug_sync();
         if (pqh_debug_sync()) PQH_HIP(ctx, hipStreamSynchronize((ctx)->stream));          \
     } while (0)
 
-// Device-side code tables shared by the encode and decode kernels (pqh_tables.hip).
+// Device-side code tables shared by the encode and decode kernels (built by pqh_tables.hip,
+// decoded by pqh_decode.hip).
 //   enc [m][items] u64: (len << 56) | code (right-aligned, len <= 56; 0 = no code)
 //   enc32 [m][items] u32: the same entry as len << 26 | code when len <= 26, else ~0u
 //   enc16 [m][items] u16: len << 12 | code when 1 <= len <= 12, 0 (no code), else 0xFFFF
@@ -177,6 +178,9 @@ bool pqh_debug_sync();
 //        are 2^w2-entry blocks at lut2[l2base + (sub << w2)] holding (len2 << 12) | sym,
 //        15 << 12 = even longer (linear search in longs), 0 = invalid
 //   longs [tables][k] {code, len, sym}, long_cnt [tables]: codes beyond both levels
+constexpr int kMaxCodeLen = 56;
+constexpr unsigned long long kCodeMask = (1ull << kMaxCodeLen) - 1;
+
 struct pqh_long_code {
     unsigned long long code;
     uint32_t len;

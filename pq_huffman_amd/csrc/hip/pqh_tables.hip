@@ -1,4 +1,5 @@
-// pqh_tables.hip -- Huffman code tables built on the GPU, and the chunked stream decoder.
+// pqh_tables.hip -- Huffman code tables built on the GPU (the stream decoder that reads
+// them: pqh_decode.hip).
 //
 //  huff_trees   huffman_codebook_init_encoder + collect_codes (huffman_encode.c:33-192,
 //               :100-132) for every (part, previous-symbol) alphabet at once: one lane per
@@ -12,11 +13,6 @@
 //  lut_build    two-level decode tables per alphabet: a first level of up to 2^11
 //               entries (2^9 in context mode, where there are K*m alphabets), second-level
 //               subtables for the prefixes of longer codes, ranges taken from a pool head.
-//  dec_chunks   huffman_decoder.c:211-255: one lane per chunk of C vectors; a symbol costs
-//               one table load instead of one trie step per bit (huffman_decode.c:137-191).
-//  sel_rows     the same decode for selected rows only: one lane per requested id, walking
-//  dec_range    its chunk from the chunk index; the cut chunks of a row range; optionally
-//               fused with the PQ reconstruction (pqh_decode_select / _range / pqh_fetch_vectors).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -28,8 +24,6 @@
 
 namespace {
 
-constexpr int kMaxCodeLen = 56;
-constexpr unsigned long long kCodeMask = (1ull << 56) - 1;
 constexpr int kL1Max = 13;                      // decode first level: 2^W1 entries, W1 <= 13
 constexpr long long kL2BaseMax = 1ll << 23;     // (meta holds l2base in 23 bits)
 
@@ -550,7 +544,7 @@ huff_trees_wave(const uint32_t* __restrict__ counts, int k, long long trees,
 }
 
 // diagnostics: s_memtime stamps of the first workgroup's phases (pqh_debug_stamps):
-// [0..6] huff_trees tree 0, [8..13] dec_chunks workgroup 0 lane 0 (g_tree_stamps, above)
+// [0..6] huff_trees tree 0 (g_tree_stamps, above)
 
 // Compact per-tree layout for K <= 256 (3.5 KB, so 32 trees fit one workgroup and the
 // whole build occupies 64 CUs -- it can run beside the next batch's assignment):
@@ -594,9 +588,6 @@ huff_trees_small(const uint32_t* __restrict__ counts, int k, long long trees,
     const uint32_t* cnt = counts + (long long)t * k;
     unsigned long long* out = enc + (long long)t * k;
     const bool stamp = blockIdx.x == 0 && t == 0;
-#ifdef PQH_LAT_PRIO   // (experiment) latency-bound waves first in issue arbitration
-    __builtin_amdgcn_s_setprio(PQH_LAT_PRIO);
-#endif
     if (stamp) g_tree_stamps[0] = __builtin_amdgcn_s_memtime();
     uint32_t* kid = kid_all + t;
     uint32_t* lcnt = kid;                      // leaf counts until the first merge
@@ -1644,946 +1635,6 @@ lut_build(const unsigned long long* __restrict__ enc, uint32_t* __restrict__ enc
     if (threadIdx.x == 0) long_cnt[t] = nlong;
 }
 
-// ------------------------------------------------------------------- decoding
-// Bit reader over a word array: a 64-bit MSB-first buffer refilled one 32-bit word at a
-// time, branch-free (the next word is always read; the array is readable up to `lim`).
-// WIN = the words are this workgroup's LDS window (the compiler then emits ds_read).
-struct BitReader {
-    const uint32_t* words;
-    long long lim;             // last readable index
-    long long next;            // next word to load
-    unsigned long long buf;
-    int have;
-    __device__ __forceinline__ uint32_t load(long long i) const {
-        return __builtin_bswap32(words[min(i, lim)]);
-    }
-    __device__ __forceinline__ void init(const uint32_t* w, long long l, unsigned long long p) {
-        words = w;
-        lim = l;
-        const long long wi = (long long)(p >> 5);
-        const int o = (int)(p & 31);
-        buf = (((unsigned long long)load(wi) << 32) | load(wi + 1)) << o;
-        have = 64 - o;
-        next = wi + 2;
-    }
-    __device__ __forceinline__ unsigned long long pos() const {
-        return (unsigned long long)next * 32 - (unsigned long long)have;
-    }
-    __device__ __forceinline__ void skip(int nb) {   // nb <= 32
-        const uint32_t w = load(next);
-        buf <<= nb;
-        have -= nb;
-        const bool need = have <= 32;
-        buf |= need ? ((unsigned long long)w << (32 - have)) : 0ull;
-        next += need ? 1 : 0;
-        have += need ? 32 : 0;
-    }
-    __device__ __forceinline__ void skip_long(int nb) {   // nb may exceed 32
-        while (nb > 0) {
-            const int step = nb < 32 ? nb : 32;
-            skip(step);
-            nb -= step;
-        }
-    }
-    __device__ __forceinline__ uint32_t peek(int nb) const { return (uint32_t)(buf >> (64 - nb)); }
-    __device__ unsigned long long peek_long(int nb) const {  // nb <= 56
-        const unsigned long long p = pos();
-        const long long wi = (long long)(p >> 5);
-        const int o = (int)(p & 31);
-        const unsigned long long hi = ((unsigned long long)load(wi) << 32) | load(wi + 1);
-        const unsigned long long lo = load(wi + 2);
-        const unsigned long long w64 = o ? ((hi << o) | (lo >> (32 - o))) : hi;
-        return w64 >> (64 - nb);
-    }
-};
-
-// Decoder tables as seen by one workgroup.
-struct DecTables {
-    const uint32_t* meta;      // LDS copy
-    const uint16_t* lut1;      // LDS copy (non-context) or global
-    const uint16_t* lut2;
-    long long lut2_cap;
-    const pqh_long_code* longs;
-    const uint32_t* long_cnt;
-    int k;
-    int w1;                    // fixed first-level width of the table set
-};
-
-// one symbol of alphabet `tab` (huffman_decode.c:137-191 as table lookups); false = invalid.
-// The L1 lookup depends only on (tab, next W1 bits); the metadata read runs beside it and
-// is needed only for the second level.
-__device__ __forceinline__ bool dec_symbol(BitReader& br, const DecTables& T, long long tab,
-                                           unsigned& sym) {
-    const int w1 = T.w1;
-    const uint16_t e = T.lut1[(tab << w1) + br.peek(w1)];
-    const uint32_t mt = T.meta[tab];
-    const int len = e >> 12;
-    sym = e & 0xFFFu;
-    if (len >= 1 && len <= w1) {
-        br.skip(len);
-        return sym < (unsigned)T.k;
-    }
-    if (len != 15) return false;
-    bool slow = true;
-    if (sym != 0xFFFu) {
-        const int w2 = (int)((mt >> 4) & 15u);
-        const long long li = (long long)(mt >> 9) + ((long long)sym << w2) +
-                             (br.peek(w1 + w2) & ((1u << w2) - 1u));
-        if (w2 < 1 || (mt & 0x100u) || li >= T.lut2_cap) return false;
-        const uint16_t e2 = T.lut2[li];
-        const int len2 = e2 >> 12;
-        if (len2 >= 1 && len2 <= w2) {
-            sym = e2 & 0xFFFu;
-            br.skip(w1 + len2);
-            slow = false;
-        } else if (len2 != 15) {
-            return false;
-        }
-    }
-    if (slow) {   // codes beyond both levels: rare, linear search
-        const uint32_t cnt = T.long_cnt[tab];
-        bool found = false;
-        for (uint32_t q = 0; q < cnt; ++q) {
-            const pqh_long_code lc = T.longs[tab * T.k + q];
-            if (br.peek_long((int)lc.len) == lc.code) {
-                sym = lc.sym;
-                br.skip_long((int)lc.len);
-                found = true;
-                break;
-            }
-        }
-        if (!found) return false;
-    }
-    return sym < (unsigned)T.k;   // never false for a well-formed table
-}
-
-// Per-lane decode of [v0, v1) in batches of S vectors staged in LDS; every lane of the
-// workgroup runs the batch loop (barriers).  `src` is the LDS window or the global stream.
-template <int MT, typename CodeT>
-__device__ __forceinline__ void decode_lanes(const uint32_t* src, long long src_lim,
-                                             unsigned long long start, bool live, long long j,
-                                             long long j0, long long jn, long long n, int m,
-                                             int k, int context, int raw_first,
-                                             int chunk_vectors, int S,
-                                             const CodeT* __restrict__ chunk_prev,
-                                             const DecTables& T, CodeT* stage,
-                                             CodeT* __restrict__ out, bool& ok) {
-    const int lane = threadIdx.x;
-    const long long v0 = j * chunk_vectors;
-    const long long v1 = min(n, v0 + chunk_vectors);
-    BitReader br;
-    br.init(src, src_lim, live ? start : 0);
-    unsigned prev[MT ? MT : 16];
-    bool warm = context && j == 0 && raw_first && live;
-#pragma unroll
-    for (int i = 0; i < (MT ? MT : 16); ++i)
-        prev[i] = (live && i < m && context && !warm) ? (unsigned)chunk_prev[j * m + i] : 0u;
-    const int roots = context ? k : 1;
-    const long long run = (long long)S * m;   // staged codes per lane per batch
-
-    for (int s0 = 0; s0 < chunk_vectors; s0 += S) {
-        long long va = v0 + s0;
-        const long long vb = live ? min(v1, va + S) : va;
-        if (warm && va < vb) {   // global row 0 of a context stream: ceil(log2 K) raw bits
-            int warm_bits = 1;   // per part (huffman_decode.c:73-76; the encoder writes 8)
-            while ((1 << warm_bits) < k) ++warm_bits;
-            for (int i = 0; i < m; ++i) {
-                prev[i] = br.peek(warm_bits);
-                br.skip(warm_bits);
-            }
-            CodeT* o = stage + lane * run;
-            for (int i = 0; i < m; ++i) o[i] = (CodeT)prev[i];
-            ++va;
-            warm = false;
-        }
-        for (long long v = va; v < vb && ok; ++v) {
-#pragma unroll
-            for (int i = 0; i < (MT ? MT : 16); ++i) {
-                if (!MT && i >= m) break;
-                const long long tab = (long long)i * roots + (context ? prev[i] : 0u);
-                unsigned sym;
-                if (!dec_symbol(br, T, tab, sym)) {
-                    ok = false;
-                    break;
-                }
-                prev[i] = sym;
-            }
-            CodeT* o = stage + lane * run + (v - v0 - s0) * m;
-            if constexpr (sizeof(CodeT) == 1 && MT % 4 == 0 && MT > 0) {
-#pragma unroll
-                for (int q = 0; q < MT / 4; ++q)
-                    reinterpret_cast<uint32_t*>(o)[q] = prev[4 * q] | (prev[4 * q + 1] << 8) |
-                                                        (prev[4 * q + 2] << 16) | (prev[4 * q + 3] << 24);
-            } else {
-#pragma unroll
-                for (int i = 0; i < (MT ? MT : 16); ++i)
-                    if (MT || i < m) o[i] = (CodeT)prev[i];
-            }
-        }
-        __syncthreads();
-        // write back: lane-run r holds rows (j0 + r) * C + s0 ... of at most S rows
-        if (S == chunk_vectors && (run * (long long)sizeof(CodeT)) % 4 == 0) {
-            // runs are contiguous: one linear copy of the workgroup's rows
-            const long long rows = min(n, (j0 + 64) * chunk_vectors) - j0 * chunk_vectors;
-            const long long nbytes = rows * m * (long long)sizeof(CodeT);
-            char* dst = reinterpret_cast<char*>(out + j0 * chunk_vectors * m);
-            const long long n4 = nbytes / 4;
-            for (long long q = lane; q < n4; q += 64)
-                __builtin_nontemporal_store(reinterpret_cast<const uint32_t*>(stage)[q],
-                                            reinterpret_cast<uint32_t*>(dst) + q);
-            for (long long q = n4 * 4 + lane; q < nbytes; q += 64)
-                dst[q] = reinterpret_cast<const char*>(stage)[q];
-        } else {
-            for (long long q = lane; q < 64 * run; q += 64) {
-                const long long r = q / run, w = q % run;
-                const long long row = (j0 + r) * chunk_vectors + s0 + w / m;
-                if (r < jn && s0 + w / m < chunk_vectors && row < n) out[row * m + w % m] = stage[q];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// One lane per chunk of C vectors (huffman_decoder.c:211-255).  The workgroup's 64 chunks
-// are contiguous in the stream, so their bits are first copied into an LDS window with
-// coalesced non-temporal loads (global fallback when the window is too small); decoded
-// codes are staged in LDS and written back coalesced, S vectors per lane at a time.  The
-// only global loads in the symbol loop are then the table lookups, and no store sits in
-// front of them in the vmcnt queue.  MT = parts at compile time (0 = runtime m <= 16).
-template <int MT, typename CodeT, bool L1_IN_LDS>
-__global__ void __launch_bounds__(64)
-dec_chunks(const uint32_t* __restrict__ words, long long nwords, long long n, int m_rt, int k,
-           int context, int raw_first, int chunk_vectors,
-           const unsigned long long* __restrict__ chunk_off, const CodeT* __restrict__ chunk_prev,
-           const uint16_t* __restrict__ lut1_g, const uint16_t* __restrict__ lut2,
-           const uint32_t* __restrict__ meta_g, int w1, long long tables, long long lut2_cap,
-           const pqh_long_code* __restrict__ longs,
-           const uint32_t* __restrict__ long_cnt, CodeT* __restrict__ out,
-           unsigned long long* __restrict__ err, int win_words, int S) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int m = MT ? MT : m_rt;
-    const long long meta_b = (tables * 4 + 15) & ~15ll;
-    const long long l1_b = L1_IN_LDS ? (((tables << w1) * 2 + 15) & ~15ll) : 0;
-    uint32_t* meta = reinterpret_cast<uint32_t*>(lds);
-    uint16_t* l1s = reinterpret_cast<uint16_t*>(lds + meta_b);
-    uint32_t* win = reinterpret_cast<uint32_t*>(lds + meta_b + l1_b);
-    CodeT* stage = reinterpret_cast<CodeT*>(lds + meta_b + l1_b + ((long long)win_words + 4) * 4);
-    const int lane = threadIdx.x;
-    const bool stamp = blockIdx.x == 0 && lane == 0;
-#ifdef PQH_LAT_PRIO   // (experiment) latency-bound waves first in issue arbitration
-    __builtin_amdgcn_s_setprio(PQH_LAT_PRIO);
-#endif
-    if (stamp) g_tree_stamps[8] = __builtin_amdgcn_s_memtime();
-    for (long long t = lane; t < tables; t += 64) meta[t] = meta_g[t];
-    if constexpr (L1_IN_LDS) {
-        const long long n16 = ((tables << w1) * 2 + 15) / 16;
-        const uint4* src = reinterpret_cast<const uint4*>(lut1_g);
-        uint4* dst = reinterpret_cast<uint4*>(l1s);
-        for (long long i = lane; i < n16; i += 64) dst[i] = src[i];
-    }
-    const long long chunks = (n + chunk_vectors - 1) / chunk_vectors;
-    const long long j0 = (long long)blockIdx.x * 64;
-    const long long jn = min(chunks - j0, 64ll);
-    if (stamp) g_tree_stamps[9] = __builtin_amdgcn_s_memtime();
-    // stream window of this workgroup's chunks
-    const unsigned long long b_lo = chunk_off[j0];
-    const unsigned long long b_hi = j0 + 64 < chunks ? chunk_off[j0 + 64] : (unsigned long long)nwords * 32;
-    const long long w_lo = (long long)(b_lo >> 5);
-    const long long w_hi = min(nwords, (long long)((b_hi + 31) >> 5) + 2);
-    const bool in_lds = w_hi - w_lo <= win_words;
-    if (in_lds) {   // streamed once: non-temporal, so the code tables keep the L2
-        const long long nw = w_hi - w_lo;
-        for (long long w0 = 0; w0 < nw; w0 += 8 * 64) {   // 8 loads in flight per lane
-            uint32_t r[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const long long w = w0 + u * 64 + lane;
-                r[u] = w < nw ? __builtin_nontemporal_load(words + w_lo + w) : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const long long w = w0 + u * 64 + lane;
-                if (w < nw) win[w] = r[u];
-            }
-        }
-        if (lane < 4) win[nw + lane] = 0;   // zero pad read past the window
-    }
-    __syncthreads();
-
-    if (stamp) {
-        g_tree_stamps[10] = __builtin_amdgcn_s_memtime();
-        g_tree_stamps[13] = in_lds;
-    }
-    DecTables T{meta, L1_IN_LDS ? l1s : lut1_g, lut2, lut2_cap, longs, long_cnt, k, w1};
-    const long long j = j0 + lane;
-    const bool live = lane < jn;
-    bool ok = true;
-    const unsigned long long start = live ? chunk_off[j] : 0;
-    if (in_lds)
-        decode_lanes<MT, CodeT>(win, w_hi - w_lo + 3, live ? start - (unsigned long long)w_lo * 32 : 0,
-                                live, j, j0, jn, n, m, k, context, raw_first, chunk_vectors, S,
-                                chunk_prev, T, stage, out, ok);
-    else
-        decode_lanes<MT, CodeT>(words, nwords - 1, start, live, j, j0, jn, n, m, k, context,
-                                raw_first, chunk_vectors, S, chunk_prev, T, stage, out, ok);
-    if (stamp) g_tree_stamps[11] = __builtin_amdgcn_s_memtime();
-    if (!ok) atomicOr(err, 1ull);
-}
-
-// ---- slim decoder for 8-part u8 rows (the bench shape): <= 32 VGPRs, so, like the table
-// builds, it runs beside the assignment grid.  One lane per chunk of C <= 32 vectors, 64
-// chunks per workgroup; the chunks' stream window in LDS (or, if it does not fit, the
-// global stream at 32-bit offsets from the window's first word); a row is decoded into one
-// u64, staged in LDS and written back as whole rows; the context row is that u64.  Table
-// lookups as dec_symbol (first level, second level, long list).
-template <bool LDS>
-struct BitRd {   // MSB-first reader over words [0, lim] (32-bit indices)
-    const uint32_t* w;
-    uint32_t lim;
-    uint32_t next;
-    unsigned long long buf;
-    int have;
-    __device__ __forceinline__ uint32_t load(uint32_t i) const { return __builtin_bswap32(w[min(i, lim)]); }
-    __device__ __forceinline__ void init(unsigned long long p) {
-        const uint32_t wi = (uint32_t)(p >> 5);
-        const int o = (int)(p & 31);
-        buf = (((unsigned long long)load(wi) << 32) | load(wi + 1)) << o;
-        have = 64 - o;
-        next = wi + 2;
-    }
-    __device__ __forceinline__ uint32_t peek(int nb) const { return (uint32_t)(buf >> (64 - nb)); }
-    __device__ __forceinline__ void skip(int nb) {   // nb <= 32
-        const uint32_t x = load(next);
-        buf <<= nb;
-        have -= nb;
-        const bool need = have <= 32;
-        buf |= need ? ((unsigned long long)x << (32 - have)) : 0ull;
-        next += need ? 1u : 0u;
-        have += need ? 32 : 0;
-    }
-    __device__ __forceinline__ unsigned long long peek56() const {   // the next 56 bits
-        const unsigned long long p = (unsigned long long)next * 32 - (unsigned long long)have;
-        const uint32_t wi = (uint32_t)(p >> 5);
-        const int o = (int)(p & 31);
-        const unsigned long long hi = ((unsigned long long)load(wi) << 32) | load(wi + 1);
-        const unsigned long long lo = load(wi + 2);
-        return (o ? ((hi << o) | (lo >> (32 - o))) : hi) >> 8;
-    }
-};
-
-// The LDS window's reader: the window holds the stream words already byte-swapped (MSB-first
-// as integers, done once when they are staged), and the reader keeps only the bit position, so
-// a peek is one two-word LDS read and a funnel shift and a skip one add (the 64-bit buffer of
-// BitRd costs ~17 VALU per skip: the refill's shifts and selects).  Words past `lim` read as
-// the last one (the window's zero pad).
-struct PosRd {
-    const uint32_t* w;
-    uint32_t lim;
-    uint32_t pos;
-    __device__ __forceinline__ uint32_t word(uint32_t i) const { return w[min(i, lim)]; }
-    __device__ __forceinline__ void init(unsigned long long p) { pos = (uint32_t)p; }
-    __device__ __forceinline__ uint32_t peek(int nb) const {   // 1 <= nb <= 32
-        // words i and i + 1 in one ds_read2 (i clamped so both are in [0, lim]: past the
-        // window's data both are its zero pad), then one 64-bit shift
-        const uint32_t i = min(pos >> 5, lim - 1);
-        const unsigned long long ab = ((unsigned long long)w[i] << 32) | w[i + 1];
-        return (uint32_t)((ab << (pos & 31u)) >> 32) >> (32 - nb);
-    }
-    __device__ __forceinline__ void skip(int nb) { pos += (uint32_t)nb; }
-    __device__ __forceinline__ unsigned long long peek56() const {   // the next 56 bits
-        const uint32_t i = pos >> 5;
-        const int o = (int)(pos & 31u);
-        const unsigned long long hi = ((unsigned long long)word(i) << 32) | word(i + 1);
-        const unsigned long long lo = word(i + 2);
-        return (o ? ((hi << o) | (lo >> (32 - o))) : hi) >> 8;
-    }
-};
-
-// codes beyond both table levels: linear search of the alphabet's long list against the
-// next 56 stream bits; returns len << 16 | sym, or 0 if none matches (inlined: a call would
-// cost the kernel its register budget)
-__device__ __forceinline__ uint32_t dec_long(const pqh_long_code* __restrict__ longs, uint32_t cnt,
-                                          unsigned long long bits56) {
-    for (uint32_t q = 0; q < cnt; ++q) {
-        const pqh_long_code lc = longs[q];
-        if (lc.len >= 1 && lc.len <= 56 && (bits56 >> (56 - lc.len)) == lc.code)
-            return (lc.len << 16) | lc.sym;
-    }
-    return 0;
-}
-
-struct Row8Tabs {
-    const uint16_t* lut1;
-    const uint16_t* lut2;
-    const uint32_t* meta;
-    const pqh_long_code* longs;
-    const uint32_t* long_cnt;
-    long long lut2_cap;
-    int w1, k;
-    int prio;   // wave issue priority (pqh_prio)
-};
-
-// one symbol of alphabet tab, or -1 (invalid)
-#ifndef PQH_DEC_SYM_OLD
-// A wave decodes 64 chains in lock step, so a branch taken by any lane costs every lane: with
-// W1 = 9 about 3 % of a SIFT batch's symbols are longer than the first level, so 87 % of the
-// wave's symbol steps run the second level.  This form keeps that path short: the alphabet's
-// meta word is loaded with the first-level entry (8 KB per table set: cache-resident), so the
-// second level is one dependent load, and every path but the long list ends in the same
-// single skip.  Same results as the round-5 form (PQH_DEC_SYM_OLD).
-template <typename Rd>
-__device__ __forceinline__ int dec_sym8(Rd& br, const Row8Tabs& T, unsigned tab) {
-    const int w1 = T.w1;
-    const uint32_t mt = T.meta[tab];
-    const uint32_t p32 = br.peek(32);   // (>= 33 bits are buffered; W1 + w2 <= 25)
-    const uint16_t e = T.lut1[(tab << w1) + (p32 >> (32 - w1))];
-    // (both loads complete here: without this the compiler sinks the meta load into the
-    // second-level branch, behind the first-level load's result)
-    asm volatile("" ::"v"(mt), "v"(e));
-    const int len = e >> 12;
-    unsigned sym = e & 0xFFFu;
-    int adv = -1;   // bits to skip; 0: the long list; -1: invalid
-    if (len >= 1 && len <= w1) {
-        adv = len;
-    } else if (len == 15) {
-        adv = 0;
-        if (sym != 0xFFFu) {   // second level
-            const int w2 = (int)((mt >> 4) & 15u);
-            const long long li = (long long)(mt >> 9) + ((long long)sym << w2) +
-                                 ((p32 >> (32 - w1 - w2)) & ((1u << w2) - 1u));
-            adv = -1;
-            if (w2 >= 1 && !(mt & 0x100u) && li < T.lut2_cap) {
-                const uint16_t e2 = T.lut2[li];
-                const int len2 = e2 >> 12;
-                if (len2 >= 1 && len2 <= w2) {
-                    adv = w1 + len2;
-                    sym = e2 & 0xFFFu;
-                } else if (len2 == 15) {
-                    adv = 0;
-                }
-            }
-        }
-    }
-    if (adv == 0) {   // codes beyond both levels: the alphabet's long list
-        const uint32_t f = dec_long(T.longs + (long long)tab * T.k, T.long_cnt[tab], br.peek56());
-        if (!f) return -1;
-        for (int nb = (int)(f >> 16); nb > 0; nb -= 32) br.skip(nb < 32 ? nb : 32);
-        sym = f & 0xFFFFu;
-        return sym < (unsigned)T.k ? (int)sym : -1;
-    }
-    if (adv < 0) return -1;
-    br.skip(adv);
-    return sym < (unsigned)T.k ? (int)sym : -1;
-}
-#else
-template <typename Rd>
-__device__ __forceinline__ int dec_sym8(Rd& br, const Row8Tabs& T, unsigned tab) {
-    const int w1 = T.w1;
-    const uint16_t e = T.lut1[(tab << w1) + br.peek(w1)];
-    const int len = e >> 12;
-    unsigned sym = e & 0xFFFu;
-    if (len >= 1 && len <= w1) {
-        br.skip(len);
-        return sym < (unsigned)T.k ? (int)sym : -1;
-    }
-    if (len != 15) return -1;
-    if (sym != 0xFFFu) {   // second level
-        const uint32_t mt = T.meta[tab];
-        const int w2 = (int)((mt >> 4) & 15u);
-        const long long li = (long long)(mt >> 9) + ((long long)sym << w2) +
-                             (br.peek(w1 + w2) & ((1u << w2) - 1u));
-        if (w2 < 1 || (mt & 0x100u) || li >= T.lut2_cap) return -1;
-        const uint16_t e2 = T.lut2[li];
-        const int len2 = e2 >> 12;
-        if (len2 >= 1 && len2 <= w2) {
-            br.skip(w1 + len2);
-            sym = e2 & 0xFFFu;
-            return sym < (unsigned)T.k ? (int)sym : -1;
-        }
-        if (len2 != 15) return -1;
-    }
-    const uint32_t f = dec_long(T.longs + (long long)tab * T.k, T.long_cnt[tab], br.peek56());
-    if (!f) return -1;
-    for (int nb = (int)(f >> 16); nb > 0; nb -= 32) br.skip(nb < 32 ? nb : 32);
-    sym = f & 0xFFFFu;
-    return sym < (unsigned)T.k ? (int)sym : -1;
-}
-
-#endif
-
-// One lane's chunk: rows of NW u64 words, SB-bit symbols packed little-end first (SB = 8:
-// u8 codes, 8 NW parts; SB = 16: u16 codes, 4 NW parts), so a row is decoded into NW
-// registers, staged in LDS and stored whole; the context row is those registers.
-template <bool CTX, bool LDS, int NW, int SB>
-__device__ __forceinline__ bool dec_row_lane(const uint32_t* src, uint32_t lim,
-                                             unsigned long long start, long long j, long long n,
-                                             int chunk_vectors, int raw_first,
-                                             const unsigned long long* __restrict__ chunk_prev,
-                                             const Row8Tabs& T, unsigned long long* st) {
-    constexpr int PW = 64 / SB;   // parts per word
-    constexpr unsigned SMASK = (1u << SB) - 1u;
-    // (LDS: the window's words are byte-swapped when staged; global: BitRd swaps per load)
-    using Rd = typename std::conditional<LDS, PosRd, BitRd<false>>::type;
-    Rd br{};
-    br.w = src;
-    br.lim = lim;
-    br.init(start);
-    const long long v0 = j * chunk_vectors;
-    const int cnt = (int)min((long long)chunk_vectors, n - v0);
-    unsigned long long prev[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) prev[w] = 0;
-    int s = 0;
-    if (CTX) {
-        if (j == 0 && raw_first) {   // global row 0: ceil(log2 K) raw bits per part
-            int wb = 1;              // (huffman_decode.c:73-76; the encoder writes 8)
-            while ((1 << wb) < T.k) ++wb;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-#pragma unroll 1
-                for (int i = 0; i < PW; ++i) {
-                    prev[w] |= (unsigned long long)br.peek(wb) << (SB * i);
-                    br.skip(wb);
-                }
-                st[w] = prev[w];
-            }
-            s = 1;
-        } else {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) prev[w] = chunk_prev[j * NW + w];
-        }
-    }
-    const unsigned roots = CTX ? (unsigned)T.k : 1u;
-    for (; s < cnt; ++s) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            unsigned long long row = 0;
-#pragma unroll 1
-            for (int i = 0; i < PW; ++i) {   // (rolled: one copy of the lookup code, fewer registers)
-                const unsigned part = (unsigned)(w * PW + i);
-                const unsigned tab =
-                    part * roots + (CTX ? (unsigned)(prev[w] >> (SB * i)) & SMASK : 0u);
-                const int sym = dec_sym8(br, T, tab);
-                if (sym < 0) return false;
-                row |= (unsigned long long)sym << (SB * i);
-            }
-            prev[w] = row;
-            st[s * NW + w] = row;
-        }
-    }
-    return true;
-}
-
-template <bool CTX, int NW, int SB>
-__global__ void __launch_bounds__(64)
-dec_rows(const uint32_t* __restrict__ words, long long nwords, long long n, int raw_first,
-         int chunk_vectors, const unsigned long long* __restrict__ chunk_off,
-         const unsigned long long* __restrict__ chunk_prev, Row8Tabs T,
-         unsigned long long* __restrict__ out, unsigned long long* __restrict__ err, int win_words) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    unsigned long long* stage = reinterpret_cast<unsigned long long*>(lds);   // [64][C][NW]
-    uint32_t* win = reinterpret_cast<uint32_t*>(lds + 64 * 8 * NW * chunk_vectors);
-    const int lane = threadIdx.x;
-    pqh_set_prio(T.prio);   // latency-bound: issue ahead of the assignment's waves
-    const long long chunks = (n + chunk_vectors - 1) / chunk_vectors;
-    const long long j0 = (long long)blockIdx.x * 64;
-    const long long jn = min(chunks - j0, 64ll);
-    const unsigned long long b_lo = chunk_off[j0];
-    const unsigned long long b_hi = j0 + 64 < chunks ? chunk_off[j0 + 64] : (unsigned long long)nwords * 32;
-    const long long w_lo = (long long)(b_lo >> 5);
-    const long long w_hi = min(nwords, (long long)((b_hi + 31) >> 5) + 2);
-    const long long nw = w_hi - w_lo;
-    const bool in_lds = nw <= win_words;
-    if (in_lds) {   // streamed once: non-temporal, so the code tables keep the L2
-#pragma unroll 1
-        for (long long w0 = 0; w0 < nw; w0 += 4 * 64) {
-            uint32_t r[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const long long w = w0 + u * 64 + lane;
-                r[u] = w < nw ? __builtin_nontemporal_load(words + w_lo + w) : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const long long w = w0 + u * 64 + lane;
-                if (w < nw) win[w] = __builtin_bswap32(r[u]);   // (MSB-first: PosRd)
-            }
-        }
-        if (lane < 4) win[nw + lane] = 0;   // zero pad read past the window
-    }
-    __syncthreads();
-    const long long j = j0 + lane;
-    bool ok = true;
-    if (lane < jn) {
-        const unsigned long long start = chunk_off[j] - (unsigned long long)w_lo * 32;
-        unsigned long long* st = stage + (long long)lane * chunk_vectors * NW;
-        ok = in_lds ? dec_row_lane<CTX, true, NW, SB>(win, (uint32_t)(nw + 3), start, j, n,
-                                                      chunk_vectors, raw_first, chunk_prev, T, st)
-                    : dec_row_lane<CTX, false, NW, SB>(words + w_lo, (uint32_t)(nwords - 1 - w_lo),
-                                                       start, j, n, chunk_vectors, raw_first,
-                                                       chunk_prev, T, st);
-    }
-    __syncthreads();
-    // the workgroup's rows are contiguous: whole-row stores
-    const long long r0 = j0 * chunk_vectors * NW;
-    const long long words_out = (min(n, (j0 + 64) * chunk_vectors) - j0 * chunk_vectors) * NW;
-#pragma unroll 1
-    for (long long q = lane; q < words_out; q += 64) __builtin_nontemporal_store(stage[q], out + r0 + q);
-    if (!ok) atomicOr(err, 1ull);
-}
-
-// ---- random access: selected rows, fused reconstruction, row ranges -------------------
-// (pqh_decode_select / pqh_fetch_vectors / pqh_decode_range).  The chunk index is the only
-// structure these need: a row is reached by walking its chunk from the chunk's bit offset,
-// in the chunk's stored context.  The ids of a wave are scattered over the stream, so there
-// is no window to stage: every lane reads the global stream through SelRd -- BitRd, based
-// at the word its chunk starts in (BitRd's 32-bit word indices then serve a stream of any
-// length) and clamped to the stream's last word.  A start past the stream is refused before
-// anything is read; the caller compares pos() with the stream's length after its walk.
-
-// BitRd whose skip loads the next word only when the buffer needs it: a load with 64
-// distinct lane addresses is what a step of these walks pays for, and only the lanes that
-// refill take part in it (dec_rows reads its window from LDS, where the branch-free refill
-// is the cheaper form)
-struct LazyRd : BitRd<false> {
-    __device__ __forceinline__ void skip(int nb) {   // nb <= 32
-        buf <<= nb;
-        have -= nb;
-        if (have <= 32) {
-            buf |= (unsigned long long)load(next) << (32 - have);
-            next += 1u;
-            have += 32;
-        }
-    }
-};
-
-struct SelRd {
-    LazyRd br;
-    unsigned long long base_bits;
-    __device__ __forceinline__ bool init(const uint32_t* words, long long nwords,
-                                         unsigned long long off) {
-        if (off > (unsigned long long)nwords * 32) return false;
-        const long long bw = min((long long)(off >> 5), nwords - 1);
-        br.w = words + bw;
-        br.lim = (uint32_t)min(nwords - 1 - bw, 0xFFFFFFF0ll);
-        base_bits = (unsigned long long)bw * 32;
-        br.init(off - base_bits);   // (at most bit 32 of the base word: the stream's end)
-        return true;
-    }
-    __device__ __forceinline__ unsigned long long pos() const {
-        return base_bits + (unsigned long long)br.next * 32 - (unsigned long long)br.have;
-    }
-};
-
-// ceil(log2 K): the raw bits per part of global row 0 (huffman_decode.c:73-76)
-__device__ __forceinline__ int warm_bits_of(int k) {
-    int wb = 1;
-    while ((1 << wb) < k) ++wb;
-    return wb;
-}
-
-// `steps` rows of one chunk, keeping only the running row: rows of NW u64 words as in
-// dec_row_lane (prev = the chunk's context row on entry, the last decoded row on return).
-template <bool CTX, int NW, int SB>
-__device__ __forceinline__ bool sel_walk_packed(LazyRd& br, const Row8Tabs& T, bool raw,
-                                                int steps, unsigned long long (&prev)[NW]) {
-    constexpr int PW = 64 / SB;
-    constexpr unsigned SMASK = (1u << SB) - 1u;
-    const unsigned roots = CTX ? (unsigned)T.k : 1u;
-    int s = 0;
-    if (CTX && raw) {
-        const int wb = warm_bits_of(T.k);
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            prev[w] = 0;
-#pragma unroll 1
-            for (int i = 0; i < PW; ++i) {
-                prev[w] |= (unsigned long long)br.peek(wb) << (SB * i);
-                br.skip(wb);
-            }
-        }
-        s = 1;
-    }
-    for (; s < steps; ++s) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            unsigned long long row = 0;
-#pragma unroll 1
-            for (int i = 0; i < PW; ++i) {
-                const unsigned part = (unsigned)(w * PW + i);
-                const unsigned tab =
-                    part * roots + (CTX ? (unsigned)(prev[w] >> (SB * i)) & SMASK : 0u);
-                const int sym = dec_sym8(br, T, tab);
-                if (sym < 0) return false;
-                row |= (unsigned long long)sym << (SB * i);
-            }
-            prev[w] = row;
-        }
-    }
-    return true;
-}
-
-// the same walk for any m <= 16: a plain loop over the parts, the running row in the lane's
-// LDS slot (row = the chunk's context row on entry)
-template <bool CTX, typename CodeT>
-__device__ __forceinline__ bool sel_walk_parts(LazyRd& br, const Row8Tabs& T, int m, bool raw,
-                                               int steps, CodeT* row) {
-    const unsigned roots = CTX ? (unsigned)T.k : 1u;
-    int s = 0;
-    if (CTX && raw) {
-        const int wb = warm_bits_of(T.k);
-        for (int i = 0; i < m; ++i) {
-            row[i] = (CodeT)br.peek(wb);
-            br.skip(wb);
-        }
-        s = 1;
-    }
-    for (; s < steps; ++s) {
-#pragma unroll 1
-        for (int i = 0; i < m; ++i) {
-            const unsigned tab = (unsigned)i * roots + (CTX ? (unsigned)row[i] : 0u);
-            const int sym = dec_sym8(br, T, tab);
-            if (sym < 0) return false;
-            row[i] = (CodeT)sym;
-        }
-    }
-    return true;
-}
-
-// One lane per requested id v (huffman_decoder.c:211-255 for the rows asked for): chunk
-// j = v / C from chunk_off[j] in the context chunk_prev[j] (raw row 0 for j = 0 when
-// raw_first), rows j*C ... v, row v into output slot q.  NW > 0: rows of NW u64 words (8 or
-// 16 u8 codes, 8 u16 codes) in registers; NW = 0: any m <= 16, per part.  The wave's 64
-// result rows are staged in LDS and stored whole (FETCH = false), or reconstructed from
-// there (FETCH: x_hat[q] = concat_i cent[i][code_i], every float row written by the whole
-// wave as consecutive 16-byte stores; the codes never reach memory).  An id outside [0, n)
-// gives a zero row and error bit 2; an invalid code, a chunk offset or a symbol past the
-// stream a zero row and error bit 1.
-template <typename CodeT, int NW, bool CTX, bool FETCH>
-__global__ void __launch_bounds__(64)
-sel_rows(const uint32_t* __restrict__ words, long long nwords, long long n, int m, int raw_first,
-         int chunk_vectors, const unsigned long long* __restrict__ chunk_off,
-         const void* __restrict__ chunk_prev, Row8Tabs T, const long long* __restrict__ ids,
-         long long count, void* __restrict__ out, long long ld_out, const float* __restrict__ cent,
-         int dsub, unsigned long long* __restrict__ err) {
-    __shared__ __attribute__((aligned(16))) unsigned char stage_b[64 * 16 * sizeof(CodeT)];
-    __shared__ unsigned char dead[64];
-    CodeT* stage = reinterpret_cast<CodeT*>(stage_b);
-    const int lane = threadIdx.x;
-    const long long q0 = (long long)blockIdx.x * 64;
-    const int rows = (int)min(64ll, count - q0);
-    CodeT* row = stage + lane * m;
-    unsigned flag = 0;
-    bool good = false;
-    if (lane < rows) {
-        const long long v = ids[q0 + lane];
-        if (v < 0 || v >= n) {
-            flag = 2;
-        } else {
-            const long long j = v / chunk_vectors;
-            const int steps = (int)(v - j * chunk_vectors) + 1;
-            const bool raw = CTX && j == 0 && raw_first;
-            SelRd rd;
-            good = rd.init(words, nwords, chunk_off[j]);
-            if (good) {
-                if constexpr (NW > 0) {
-                    unsigned long long prev[NW];
-#pragma unroll
-                    for (int w = 0; w < NW; ++w)
-                        prev[w] = (CTX && !raw)
-                                      ? static_cast<const unsigned long long*>(chunk_prev)[j * NW + w]
-                                      : 0ull;
-                    good = sel_walk_packed<CTX, NW, 8 * (int)sizeof(CodeT)>(rd.br, T, raw, steps, prev);
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) reinterpret_cast<unsigned long long*>(row)[w] = prev[w];
-                } else {
-                    for (int i = 0; i < m; ++i)
-                        row[i] = (CTX && !raw) ? static_cast<const CodeT*>(chunk_prev)[j * m + i]
-                                               : (CodeT)0;
-                    good = sel_walk_parts<CTX, CodeT>(rd.br, T, m, raw, steps, row);
-                }
-                good = good && rd.pos() <= (unsigned long long)nwords * 32;
-            }
-            if (!good) flag = 1;
-        }
-    }
-    if (!good)
-        for (int i = 0; i < m; ++i) row[i] = (CodeT)0;
-    dead[lane] = good ? 0 : 1;
-    if (flag) atomicOr(err, (unsigned long long)flag);
-    lds_barrier();
-    if constexpr (!FETCH) {
-        // the workgroup's rows are contiguous in the output: whole-row stores
-        const long long nbytes = (long long)rows * m * (long long)sizeof(CodeT);
-        unsigned char* dst = static_cast<unsigned char*>(out) + q0 * m * (long long)sizeof(CodeT);
-        long long done = 0;
-        if (!(reinterpret_cast<uintptr_t>(dst) & 3u)) {
-            done = nbytes & ~3ll;
-            for (long long q = lane; q < done / 4; q += 64)
-                reinterpret_cast<uint32_t*>(dst)[q] = reinterpret_cast<const uint32_t*>(stage_b)[q];
-        }
-        for (long long q = done + lane; q < nbytes; q += 64) dst[q] = stage_b[q];
-    } else {
-        float* o = static_cast<float*>(out) + q0 * ld_out;
-        const int d = m * dsub;
-        const long long k = T.k;
-        if (!(d & 3) && !(ld_out & 3) && !(reinterpret_cast<uintptr_t>(out) & 15u)) {
-            const int per = d >> 2;   // 16-byte pieces of a row; a piece may span two parts
-            for (int it = lane; it < rows * per; it += 64) {
-                const int r = it / per, c = (it - r * per) * 4;
-                const CodeT* cr = stage + r * m;
-                float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!dead[r]) {
-                    if (!(dsub & 3)) {
-                        const int i = c / dsub;
-                        val = *reinterpret_cast<const float4*>(cent + (i * k + cr[i]) * dsub + (c - i * dsub));
-                    } else {
-                        float e[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int i = (c + u) / dsub;
-                            e[u] = cent[(i * k + cr[i]) * dsub + (c + u - i * dsub)];
-                        }
-                        val = make_float4(e[0], e[1], e[2], e[3]);
-                    }
-                }
-                *reinterpret_cast<float4*>(o + (long long)r * ld_out + c) = val;
-            }
-        } else {
-            for (int it = lane; it < rows * d; it += 64) {
-                const int r = it / d, c = it - r * d;
-                const int i = c / dsub;
-                o[(long long)r * ld_out + c] =
-                    dead[r] ? 0.f : cent[(i * k + stage[r * m + i]) * dsub + (c - i * dsub)];
-            }
-        }
-    }
-}
-
-// Rows [first, first + count) where they are not whole chunks: one lane per chunk, as
-// dec_rows, walking its chunk from the start and storing only the rows inside the range
-// (the first and the last chunk of a range may be cut; the whole chunks between them go
-// through pqh_decode's kernels, skipped here as [skip_at, skip_at + skip_len)).  The running
-// row is the lane's LDS slot; a failed chunk's rows of the range are zeroed.
-template <typename CodeT, bool CTX>
-__global__ void __launch_bounds__(64)
-dec_range(const uint32_t* __restrict__ words, long long nwords, long long n, int m, int raw_first,
-          int chunk_vectors, const unsigned long long* __restrict__ chunk_off,
-          const CodeT* __restrict__ chunk_prev, Row8Tabs T, long long first, long long count,
-          long long jbeg, long long skip_at, long long skip_len, long long lanes,
-          CodeT* __restrict__ out, unsigned long long* __restrict__ err) {
-    __shared__ CodeT stage[64 * 16];
-    const long long idx = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (idx >= lanes) return;   // (no barriers below: lanes are independent)
-    long long j = jbeg + idx;
-    if (j >= skip_at) j += skip_len;
-    const long long v0 = j * chunk_vectors;
-    const long long lo = max(v0, first);
-    const long long hi = min(min(n, v0 + chunk_vectors), first + count);
-    if (lo >= hi) return;
-    CodeT* row = stage + threadIdx.x * m;
-    const bool raw = CTX && j == 0 && raw_first;
-    for (int i = 0; i < m; ++i) row[i] = (CTX && !raw) ? chunk_prev[j * m + i] : (CodeT)0;
-    const unsigned roots = CTX ? (unsigned)T.k : 1u;
-    const int wb = warm_bits_of(T.k);
-    SelRd rd;
-    bool ok = rd.init(words, nwords, chunk_off[j]);
-    for (long long v = v0; v < hi && ok; ++v) {
-#pragma unroll 1
-        for (int i = 0; i < m; ++i) {
-            int sym;
-            if (raw && v == v0) {
-                sym = (int)rd.br.peek(wb);
-                rd.br.skip(wb);
-            } else {
-                sym = dec_sym8(rd.br, T, (unsigned)i * roots + (CTX ? (unsigned)row[i] : 0u));
-            }
-            if (sym < 0) {
-                ok = false;
-                break;
-            }
-            row[i] = (CodeT)sym;
-        }
-        if (ok && v >= lo)
-            for (int i = 0; i < m; ++i) out[(v - first) * m + i] = row[i];
-    }
-    if (ok && rd.pos() > (unsigned long long)nwords * 32) ok = false;
-    if (!ok) {
-        for (long long q = (lo - first) * m; q < (hi - first) * m; ++q) out[q] = (CodeT)0;
-        atomicOr(err, 1ull);
-    }
-}
-
-// the chunk offsets handed to pqh_decode's kernels by pqh_decode_range: within the stream
-// and not decreasing, else the decode error (those kernels clamp their reads but report only
-// invalid codes)
-__global__ void __launch_bounds__(256)
-chk_offsets(const unsigned long long* __restrict__ off, long long cnt, int last_has_next,
-            unsigned long long total_bits, unsigned long long* __restrict__ err) {
-    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= cnt) return;
-    const unsigned long long a = off[j];
-    const bool next = j + 1 < cnt || last_has_next;
-    if (a > total_bits || (next && a > off[j + 1])) atomicOr(err, 1ull);
-}
-
-// argument checks shared by the random-access calls
-int sel_check(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
-              unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
-              const unsigned long long* d_chunk_offsets, const void* d_chunk_prev, long long count,
-              const void* d_out) {
-    if (!ctx || !t || n < 0 || chunk_vectors <= 0 || count < 0) return PQH_ERR_ARG;
-    if (count > 0 && (!d_out || (n > 0 && (!d_stream || !d_chunk_offsets || stream_bytes < 4))))
-        return PQH_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
-    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
-    if (t->m > 16 || (t->context && t->k > 256)) return PQH_ERR_UNSUPPORTED;
-    return pqh_use_device(ctx);
-}
-
-Row8Tabs sel_tabs(const pqh_tables_t* t) {
-    return Row8Tabs{t->d_lut1, t->d_lut2, t->d_meta, t->d_long, t->d_long_cnt, t->lut2_cap,
-                    t->l1_bits, t->k, 0};
-}
-
-// sel_rows over `count` ids: codes [count][m] (FETCH = false) or float rows ld_out apart
-template <bool FETCH>
-int sel_launch(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
-               unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
-               const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
-               const long long* d_ids, long long count, void* d_out, long long ld_out,
-               const float* d_cent, int dsub) {
-    const int esz = t->k <= 256 ? 1 : 2;
-    const int row_bytes = t->m * esz;
-    // rows of whole u64 words in registers (the shapes of dec_rows), else the per-part walk
-    const bool packed = (row_bytes == 8 || row_bytes == 16) && (esz == 1 || t->m == 8) &&
-                        !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
-    const int nw_row = packed ? row_bytes / 8 : 0;
-    const Row8Tabs T = sel_tabs(t);
-    const uint32_t* wp = reinterpret_cast<const uint32_t*>(d_stream);
-    const long long nwords = (long long)(stream_bytes / 4);
-    const unsigned blocks = (unsigned)((count + 63) / 64);
-#define PQH_SEL(CT, NW, CTX)                                                                     \
-    hipLaunchKernelGGL((sel_rows<CT, NW, CTX, FETCH>), dim3(blocks), dim3(64), 0, ctx->stream,   \
-                       wp, nwords, n, t->m, raw_first, chunk_vectors, d_chunk_offsets,           \
-                       d_chunk_prev, T, d_ids, count, d_out, ld_out, d_cent, dsub,               \
-                       ctx->d_diag + 1)
-    if (esz == 2) {
-        if (nw_row) PQH_SEL(uint16_t, 2, false); else PQH_SEL(uint16_t, 0, false);
-    } else if (t->context) {
-        if (nw_row == 1) PQH_SEL(uint8_t, 1, true);
-        else if (nw_row == 2) PQH_SEL(uint8_t, 2, true);
-        else PQH_SEL(uint8_t, 0, true);
-    } else {
-        if (nw_row == 1) PQH_SEL(uint8_t, 1, false);
-        else if (nw_row == 2) PQH_SEL(uint8_t, 2, false);
-        else PQH_SEL(uint8_t, 0, false);
-    }
-#undef PQH_SEL
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
-}
-
 // diagnostics only (pqh_debug_poison_lds): fills a whole CU's LDS (160 KB) with `value`, so a
 // kernel launched after it on any CU finds that pattern, not zeros or an earlier kernel's
 // data, in whatever LDS it reads before writing -- a test for stale-LDS reads
@@ -2965,387 +2016,4 @@ int pqh_tables_codebooks(pqh_ctx_t* ctx, const pqh_tables_t* t, huffman_codebook
     return PQH_OK;
 }
 
-int pqh_decode(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
-               unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
-               const unsigned long long* d_chunk_offsets, const void* d_chunk_prev, void* d_codes) {
-    if (!ctx || !t || n < 0 || chunk_vectors <= 0 ||
-        (n > 0 && (!d_stream || !d_chunk_offsets || !d_codes)))
-        return PQH_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
-    if (t->context && !raw_first && !d_chunk_prev) return PQH_ERR_ARG;
-    if (t->m > 16) return PQH_ERR_UNSUPPORTED;
-    int rc = pqh_use_device(ctx);
-    if (rc) return rc;
-    if (n == 0) return PQH_OK;
-    // (no memset: d_diag[1] is sticky until pqh_decode_status reads it)
-    const long long chunks = (n + chunk_vectors - 1) / chunk_vectors;
-    const long long nwords = (long long)(stream_bytes / 4);
-    const unsigned blocks = (unsigned)((chunks + 63) / 64);
-    if (reinterpret_cast<uintptr_t>(d_codes) & 3u) return PQH_ERR_ARG;
-    const size_t l1_bytes = (size_t)(t->tables << t->l1_bits) * 2;
-    const size_t meta_bytes = ((size_t)t->tables * 4 + 15) & ~(size_t)15;
-    const bool lds_l1 = meta_bytes + l1_bytes <= 48 * 1024;
-    const size_t esz = t->k <= 256 ? 1 : 2;
-    // stream window: the workgroup's 64 chunks at up to 12 (K <= 256; Huffman averages
-    // at most ~8.x bits) or 14 bits per symbol, at most 16 KB -- a larger span reads the
-    // global stream instead; staging: S vectors per lane, at most 16 KB
-    const long long sym_bits = t->k <= 256 ? 12 : 14;
-    const int win_words = (int)std::min<long long>(4096, std::max<long long>(
-        256, (64ll * chunk_vectors * t->m * sym_bits + 31) / 32 + 8));
-    int S = chunk_vectors;
-    while (S > 1 && (size_t)64 * S * t->m * esz > 16 * 1024) S = (S + 1) / 2;
-    const size_t lds = meta_bytes + (lds_l1 ? ((l1_bytes + 15) & ~(size_t)15) : 0) +
-                       ((size_t)win_words + 4) * 4 + (size_t)64 * S * t->m * esz + 16;
-    if (lds > 160 * 1024) return PQH_ERR_UNSUPPORTED;
-    // whole-row decoders (<= 32 VGPRs: they run beside the assignment grid): rows of 8 or 16
-    // u8 codes, or of 8 u16 codes, chunks of C <= 32 vectors, 8-byte aligned rows
-    const int esz_b = (int)esz;
-    const int row_bytes = t->m * esz_b;
-    if ((row_bytes == 8 || row_bytes == 16) && (esz_b == 1 || t->m == 8) && chunk_vectors <= 32 &&
-        nwords < (1ll << 31) && !(reinterpret_cast<uintptr_t>(d_codes) & 7) &&
-        !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7)) {
-        const int nw_row = row_bytes / 8;
-        const int ww = (int)std::min<long long>(4096 - 1024 * (nw_row - 1), std::max<long long>(
-            256, (64ll * chunk_vectors * t->m * sym_bits + 31) / 32 + 8));
-        const size_t lds_r = (size_t)64 * row_bytes * chunk_vectors + ((size_t)ww + 4) * 4;
-        const Row8Tabs T{t->d_lut1, t->d_lut2, t->d_meta, t->d_long, t->d_long_cnt, t->lut2_cap,
-                         t->l1_bits, t->k, pqh_prio("DECODE", 3)};
-        const uint32_t* wp = reinterpret_cast<const uint32_t*>(d_stream);
-        const unsigned long long* cp = static_cast<const unsigned long long*>(d_chunk_prev);
-        unsigned long long* op = static_cast<unsigned long long*>(d_codes);
-#define PQH_DEC_ROWS(CTX, NW, SB)                                                               \
-    do {                                                                                         \
-        if (lds_r > 64 * 1024)                                                                   \
-            PQH_HIP(ctx, hipFuncSetAttribute((const void*)(dec_rows<CTX, NW, SB>),               \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                             (int)lds_r));                                       \
-        hipLaunchKernelGGL((dec_rows<CTX, NW, SB>), dim3(blocks), dim3(64), lds_r, ctx->stream,   \
-                           wp, nwords, n, raw_first, chunk_vectors, d_chunk_offsets, cp, T, op,  \
-                           ctx->d_diag + 1, ww);                                                 \
-    } while (0)
-        if (esz_b == 2)
-            PQH_DEC_ROWS(false, 2, 16);
-        else if (nw_row == 1 && t->context)
-            PQH_DEC_ROWS(true, 1, 8);
-        else if (nw_row == 1)
-            PQH_DEC_ROWS(false, 1, 8);
-        else if (t->context)
-            PQH_DEC_ROWS(true, 2, 8);
-        else
-            PQH_DEC_ROWS(false, 2, 8);
-#undef PQH_DEC_ROWS
-        PQH_LAUNCH_CHECK(ctx);
-        return PQH_OK;
-    }
-#define PQH_DEC(MT, T, L)                                                                        \
-    do {                                                                                         \
-        if (lds > 64 * 1024)                                                                     \
-            PQH_HIP(ctx, hipFuncSetAttribute((const void*)(dec_chunks<MT, T, L>),                \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                             (int)lds));                                         \
-        hipLaunchKernelGGL((dec_chunks<MT, T, L>), dim3(blocks), dim3(64), lds, ctx->stream,      \
-                           reinterpret_cast<const uint32_t*>(d_stream), nwords, n, t->m, t->k,   \
-                           t->context, raw_first, chunk_vectors, d_chunk_offsets,                \
-                           static_cast<const T*>(d_chunk_prev), t->d_lut1, t->d_lut2, t->d_meta, \
-                           t->l1_bits, t->tables, t->lut2_cap, t->d_long,                        \
-                           t->d_long_cnt, static_cast<T*>(d_codes), ctx->d_diag + 1, win_words,  \
-                           S);                                                                   \
-    } while (0)
-    if (t->k <= 256) {
-        if (t->m == 8) {
-            if (lds_l1) PQH_DEC(8, uint8_t, true); else PQH_DEC(8, uint8_t, false);
-        } else if (t->m == 16) {
-            if (lds_l1) PQH_DEC(16, uint8_t, true); else PQH_DEC(16, uint8_t, false);
-        } else {
-            if (lds_l1) PQH_DEC(0, uint8_t, true); else PQH_DEC(0, uint8_t, false);
-        }
-    } else {
-        if (lds_l1) PQH_DEC(0, uint16_t, true); else PQH_DEC(0, uint16_t, false);
-    }
-#undef PQH_DEC
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
-}
-
-int pqh_decode_status(pqh_ctx_t* ctx) {
-    unsigned long long e = 0;
-    PQH_HIP(ctx, hipMemcpyAsync(&e, ctx->d_diag + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    PQH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (e) PQH_HIP(ctx, hipMemsetAsync(ctx->d_diag + 1, 0, 8, ctx->stream));   // (sticky until read)
-    // bit 0: an invalid code (every decoder); bit 1: an id outside the rows (pqh_decode_select,
-    // pqh_fetch_vectors) -- reported only when no code was invalid
-    if (e & 1ull) return pqh_set_error(ctx, PQH_ERR_CORRUPT, "invalid code in stream");
-    return e ? pqh_set_error(ctx, PQH_ERR_ARG, "row id outside the stream's rows") : PQH_OK;
-}
-
-int pqh_decode_select(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
-                      unsigned long long stream_bytes, long long n, int raw_first,
-                      int chunk_vectors, const unsigned long long* d_chunk_offsets,
-                      const void* d_chunk_prev, const long long* d_ids, long long count,
-                      void* d_codes) {
-    int rc = sel_check(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
-                       d_chunk_offsets, d_chunk_prev, count, d_codes);
-    if (rc) return rc;
-    if (count == 0) return PQH_OK;
-    if (!d_ids) return PQH_ERR_ARG;
-    return sel_launch<false>(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
-                             d_chunk_offsets, d_chunk_prev, d_ids, count, d_codes, 0, nullptr, 0);
-}
-
-int pqh_fetch_vectors(pqh_ctx_t* ctx, const pqh_tables_t* t, const pqh_pq_t* pq,
-                      const unsigned char* d_stream, unsigned long long stream_bytes, long long n,
-                      int raw_first, int chunk_vectors, const unsigned long long* d_chunk_offsets,
-                      const void* d_chunk_prev, const long long* d_ids, long long count,
-                      float* d_out, long long ld_out) {
-    int m = 0, k = 0, dsub = 0;
-    const float* d_cent = nullptr;
-    if (!t || pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || m != t->m || k != t->k ||
-        ld_out < (long long)m * dsub)
-        return PQH_ERR_ARG;
-    int rc = sel_check(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
-                       d_chunk_offsets, d_chunk_prev, count, d_out);
-    if (rc) return rc;
-    if (count == 0) return PQH_OK;
-    if (!d_ids || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return PQH_ERR_ARG;
-    return sel_launch<true>(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
-                            d_chunk_offsets, d_chunk_prev, d_ids, count, d_out, ld_out, d_cent,
-                            dsub);
-}
-
-int pqh_decode_range(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
-                     unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
-                     const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
-                     long long first, long long count, void* d_codes) {
-    int rc = sel_check(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
-                       d_chunk_offsets, d_chunk_prev, count, d_codes);
-    if (rc) return rc;
-    if (first < 0 || first > n - count) return PQH_ERR_ARG;
-    if (count == 0) return PQH_OK;
-    const long long C = chunk_vectors;
-    const int esz = t->k <= 256 ? 1 : 2;
-    if (reinterpret_cast<uintptr_t>(d_codes) & (uintptr_t)(esz - 1)) return PQH_ERR_ARG;
-    const long long chunks = (n + C - 1) / C;
-    const long long end = first + count;
-    const long long j_lo = first / C, j_hi = (end - 1) / C;
-    // the whole chunks [ja, jb) of the range go through pqh_decode (its windowed kernels, with
-    // the index pointers moved to chunk ja); the cut chunks at either end -- and every chunk
-    // when that output would not be 4-byte aligned -- through dec_range
-    long long ja = j_lo + (first % C ? 1 : 0);
-    long long jb = j_hi + 1 - ((end % C && end != n) ? 1 : 0);
-    unsigned char* o_in = static_cast<unsigned char*>(d_codes) + (ja * C - first) * t->m * esz;
-    if (jb <= ja || (reinterpret_cast<uintptr_t>(o_in) & 3u)) jb = ja = j_hi + 1;
-    if (jb > ja) {
-        const unsigned char* cp = static_cast<const unsigned char*>(d_chunk_prev);
-        rc = pqh_decode(ctx, t, d_stream, stream_bytes, std::min(n, jb * C) - ja * C,
-                        ja == 0 ? raw_first : 0, chunk_vectors, d_chunk_offsets + ja,
-                        cp ? cp + ja * t->m * esz : nullptr, o_in);
-        if (rc == PQH_ERR_UNSUPPORTED) {   // (a chunk too long for its staging)
-            jb = ja = j_hi + 1;
-        } else if (rc) {
-            return rc;
-        } else {
-            const long long cnt = jb - ja;
-            hipLaunchKernelGGL(chk_offsets, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0,
-                               ctx->stream, d_chunk_offsets + ja, cnt, jb < chunks ? 1 : 0,
-                               (stream_bytes / 4) * 32ull, ctx->d_diag + 1);
-        }
-    }
-    const long long lanes = (j_hi - j_lo + 1) - (jb - ja);
-    if (lanes > 0) {
-        const Row8Tabs T = sel_tabs(t);
-        const unsigned blocks = (unsigned)((lanes + 63) / 64);
-#define PQH_RANGE(CT, CTX)                                                                       \
-    hipLaunchKernelGGL((dec_range<CT, CTX>), dim3(blocks), dim3(64), 0, ctx->stream,             \
-                       reinterpret_cast<const uint32_t*>(d_stream), (long long)(stream_bytes / 4), \
-                       n, t->m, raw_first, chunk_vectors, d_chunk_offsets,                       \
-                       static_cast<const CT*>(d_chunk_prev), T, first, count, j_lo, ja, jb - ja, \
-                       lanes, static_cast<CT*>(d_codes), ctx->d_diag + 1)
-        if (esz == 2) PQH_RANGE(uint16_t, false);
-        else if (t->context) PQH_RANGE(uint8_t, true);
-        else PQH_RANGE(uint8_t, false);
-#undef PQH_RANGE
-    }
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
-}
-
-// Chunk index of a stream that came without a sidecar: a sequential walk over a HOST copy
-// of the code table (index building only; the symbols are decoded by pqh_decode).
-int pqh_chunk_index_host(const pqh_tables_t* t, const unsigned char* stream,
-                         unsigned long long stream_bytes, long long n, int raw_first,
-                         int chunk_vectors, unsigned long long* chunk_offsets, void* chunk_prev) {
-    if (!t || n < 0 || chunk_vectors <= 0 || (n > 0 && (!stream || !chunk_offsets))) return PQH_ERR_ARG;
-    if (t->context && !chunk_prev) return PQH_ERR_ARG;
-    pqh_ctx* ctx = t->ctx;
-    std::vector<unsigned long long> enc((size_t)t->m * t->items);
-    PQH_HIP(ctx, hipMemcpyAsync(enc.data(), t->d_enc, enc.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PQH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // per-table canonical lookup: (len, code) -> symbol, via sorted vectors per length
-    const int W = 16;
-    std::vector<int32_t> lut((size_t)t->tables << W, -1);
-    std::vector<std::vector<std::pair<unsigned long long, int>>> longs(t->tables);
-    for (long long tab = 0; tab < t->tables; ++tab)
-        for (int s = 0; s < t->k; ++s) {
-            const unsigned long long v = enc[(size_t)tab * t->k + s];
-            const int L = (int)(v >> 56);
-            if (!L) continue;
-            const unsigned long long code = v & kCodeMask;
-            if (L <= W) {
-                for (unsigned long long e = code << (W - L); e < (code + 1) << (W - L); ++e)
-                    lut[((size_t)tab << W) + e] = (L << 16) | s;
-            } else {
-                longs[tab].push_back({(code << 8) | (unsigned long long)L, s});
-            }
-        }
-    const unsigned long long total = stream_bytes * 8;
-    auto peek = [&](unsigned long long p, int nb) -> unsigned long long {
-        unsigned long long r = 0;
-        for (int b = 0; b < nb; ++b) {
-            const unsigned long long q = p + b;
-            r = (r << 1) | (q < total ? (unsigned long long)((stream[q >> 3] >> (7 - (q & 7))) & 1u) : 0ull);
-        }
-        return r;
-    };
-    std::vector<unsigned> prev(t->m, 0);
-    bool warm = t->context && raw_first;
-    int warm_bits = 1;
-    while ((1 << warm_bits) < t->k) ++warm_bits;
-    unsigned long long pos = 0;
-    for (long long v = 0; v < n; ++v) {
-        if (v % chunk_vectors == 0) {
-            const long long j = v / chunk_vectors;
-            chunk_offsets[j] = pos;
-            if (t->context)
-                for (int i = 0; i < t->m; ++i) {
-                    if (t->k <= 256) static_cast<uint8_t*>(chunk_prev)[j * t->m + i] = (uint8_t)prev[i];
-                    else static_cast<uint16_t*>(chunk_prev)[j * t->m + i] = (uint16_t)prev[i];
-                }
-        }
-        for (int i = 0; i < t->m; ++i) {
-            unsigned sym;
-            if (warm) {
-                sym = (unsigned)peek(pos, warm_bits);
-                pos += warm_bits;
-            } else {
-                const long long tab = (long long)i * t->roots + (t->context ? prev[i] : 0);
-                const int32_t e = lut[((size_t)tab << W) + peek(pos, W)];
-                if (e >= 0) {
-                    pos += (unsigned)e >> 16;
-                    sym = (unsigned)e & 0xFFFFu;
-                } else {
-                    bool found = false;
-                    sym = 0;
-                    for (auto& lc : longs[tab]) {
-                        const int L = (int)(lc.first & 0xFF);
-                        if (peek(pos, L) == (lc.first >> 8)) {
-                            pos += L;
-                            sym = (unsigned)lc.second;
-                            found = true;
-                            break;
-                        }
-                    }
-                    if (!found) return PQH_ERR_CORRUPT;
-                }
-                if (pos > total) return PQH_ERR_CORRUPT;
-            }
-            prev[i] = sym;
-        }
-        warm = false;
-    }
-    return PQH_OK;
-}
-
 }  // extern "C"
-
-// ---------------------------------------------------------------- tree-mode decode
-// huffman_decoder --tree (huffman_decoder.c:214-247): row p is decoded in the context of the
-// row at stream position parent_pos[p] (the traverser replayed over the children stream),
-// a root starting every part with the raw warm-up bits.  One lane per chunk of C rows from
-// the encoder's chunk index; the chunk's rows are staged in LDS, so a parent inside the
-// chunk is read back from there, and the parents that lie before the chunk come from the
-// ext sidecar (ext_rows[ext_off[j] ...], in row order) -- every chunk decodes independently.
-namespace {
-__global__ void __launch_bounds__(64)
-dec_tree(const uint32_t* __restrict__ words, long long nwords, long long n, int m, int k,
-         int chunk_vectors, const unsigned long long* __restrict__ chunk_off,
-         const long long* __restrict__ parent_pos, const long long* __restrict__ ext_off,
-         const uint8_t* __restrict__ ext_rows, const uint16_t* __restrict__ lut1,
-         const uint16_t* __restrict__ lut2, const uint32_t* __restrict__ meta, int w1,
-         long long lut2_cap, const pqh_long_code* __restrict__ longs,
-         const uint32_t* __restrict__ long_cnt, uint8_t* __restrict__ out,
-         unsigned long long* __restrict__ err, unsigned long long total_bits) {
-    extern __shared__ uint8_t tstage[];   // [64 lanes][C rows][m]
-    const long long chunks = (n + chunk_vectors - 1) / chunk_vectors;
-    const long long j = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (j >= chunks) return;               // no barriers below: lanes are independent
-    const long long v0 = j * chunk_vectors;
-    const long long v1 = min(n, v0 + chunk_vectors);
-    uint8_t* st = tstage + (long long)threadIdx.x * chunk_vectors * m;
-    DecTables T{meta, lut1, lut2, lut2_cap, longs, long_cnt, k, w1};
-    BitReader br;
-    br.init(words, nwords - 1, chunk_off[j]);
-    long long e = ext_off[j];
-    const long long e_end = ext_off[j + 1];
-    int warm_bits = 1;
-    while ((1 << warm_bits) < k) ++warm_bits;
-    // a chunk that starts past the stream's end (a truncated file or a stale sidecar) reads
-    // nothing; one whose symbols run past it is reported below -- never decoded silently
-    bool ok = chunk_off[j] <= total_bits;
-    for (long long p = v0; p < v1 && ok; ++p) {
-        const long long pp = parent_pos[p];
-        const uint8_t* prow = nullptr;
-        if (pp >= v0 && pp < p) {
-            prow = st + (pp - v0) * m;
-        } else if (pp >= 0) {
-            if (pp >= p || e >= e_end) { ok = false; break; }   // inconsistent sidecar
-            prow = ext_rows + e * m;
-            ++e;
-        }
-        uint8_t* o = st + (p - v0) * m;
-        for (int i = 0; i < m; ++i) {
-            unsigned sym;
-            if (!prow) {
-                sym = br.peek(warm_bits);
-                br.skip(warm_bits);
-            } else if (!dec_symbol(br, T, (long long)i * k + prow[i], sym)) {
-                ok = false;
-                break;
-            }
-            o[i] = (uint8_t)sym;
-        }
-    }
-    if (br.pos() > total_bits) ok = false;
-    const long long nb = (v1 - v0) * m;
-    uint8_t* dst = out + v0 * m;
-    for (long long q = 0; q < nb; ++q) dst[q] = ok ? st[q] : 0;
-    if (!ok) atomicOr(err, 1ull);
-}
-}  // namespace
-
-int pqh_decode_tree(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
-                    unsigned long long stream_bytes, long long n, int chunk_vectors,
-                    const unsigned long long* d_chunk_offsets, const long long* d_parent_pos,
-                    const long long* d_ext_offsets, const unsigned char* d_ext_rows,
-                    void* d_rows) {
-    if (!ctx || !t || !t->context || t->k > 256 || n < 0 || chunk_vectors <= 0 ||
-        (n > 0 && (!d_stream || !d_chunk_offsets || !d_parent_pos || !d_ext_offsets || !d_rows)))
-        return PQH_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
-    const size_t lds = (size_t)64 * chunk_vectors * t->m;
-    if (lds > 160 * 1024) return PQH_ERR_UNSUPPORTED;
-    int rc = pqh_use_device(ctx);
-    if (rc) return rc;
-    if (n == 0) return PQH_OK;
-    const long long chunks = (n + chunk_vectors - 1) / chunk_vectors;
-    if (lds > 64 * 1024)
-        PQH_HIP(ctx, hipFuncSetAttribute((const void*)dec_tree,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(dec_tree, dim3((unsigned)((chunks + 63) / 64)), dim3(64), lds, ctx->stream,
-                       reinterpret_cast<const uint32_t*>(d_stream), (long long)((stream_bytes + 3) / 4),
-                       n, t->m, t->k, chunk_vectors, d_chunk_offsets, d_parent_pos,
-                       d_ext_offsets, d_ext_rows, t->d_lut1, t->d_lut2, t->d_meta, t->l1_bits,
-                       t->lut2_cap, t->d_long, t->d_long_cnt, static_cast<uint8_t*>(d_rows),
-                       ctx->d_diag + 1, stream_bytes * 8ull);
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
-}

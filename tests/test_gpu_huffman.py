@@ -213,6 +213,56 @@ def test_corrupt_stream_is_reported(gpu):
     codec.decode_status(ctx)
 
 
+@pytest.mark.parametrize("chunk,window_words", [(32, 3072), (64, 4096)])
+@pytest.mark.parametrize("ctxm", [True, False])
+def test_decode_stream_window_fallback(gpu, ctxm, chunk, window_words):
+    """A workgroup's 64 chunks longer than its LDS stream window, so the lanes read the global
+    stream instead: 16-part rows in chunks of 32 (the whole-row decoder, a window of 3,072
+    words) and of 64 (the general decoder, 4,096 words)."""
+    torch, codec, ctx = gpu
+    n, m = 4096 + 5, 16
+    codes = np.random.default_rng(16).integers(0, 256, (n, m)).astype(np.uint8)
+    cd, cbs = _codebooks_from_gpu_hist(gpu, codes, 256, ctxm)
+    tabs = codec.Tables.from_codebooks(ctx, cbs)
+    enc = codec.encode(ctx, tabs, cd, chunk_vectors=chunk)
+    # the first workgroup is a full one: its chunks [0, 64) do not fit the window
+    assert n > 64 * chunk
+    off = enc.chunk_offsets.cpu().numpy()
+    assert int(off[64]) <= enc.bits
+    assert int(off[64] - off[0]) > 32 * window_words, (int(off[64]), enc.bits)
+    dec = codec.decode(ctx, tabs, enc)
+    codec.decode_status(ctx)
+    assert np.array_equal(dec.cpu().numpy(), codes)
+
+
+@pytest.mark.parametrize("chunk", [7, 64])
+def test_decode_long_codes_three_parts(gpu, chunk):
+    """The general decoder (m = 3: no whole-row form applies) through the long-code list: the
+    fib32ctx tables of test_select_long_codes, codes of up to 31 bits."""
+    torch, codec, ctx = gpu
+    fix = golden("codebooks.npz")["fib32ctx__counts"].reshape(32, 32)
+    m, k, n = 3, 256, 2000
+    counts = np.zeros((m, k, k))
+    counts[:, :32, :32] = fix
+    cbs = codec.Codebooks(counts.reshape(m, k * k), k, True)
+    tabs = codec.Tables.from_codebooks(ctx, cbs)
+    live = [p for p in range(32) if fix[p].sum() > 0]
+    nxt = {p: [c for c in live if fix[p, c] > 0] for p in live}
+    rng = np.random.default_rng(11)
+    codes = np.zeros((n, m), np.uint8)
+    codes[0] = rng.choice(live, m)
+    for v in range(1, n):
+        for i in range(m):
+            codes[v, i] = rng.choice(nxt[int(codes[v - 1, i])])
+    lens = cbs.lengths().reshape(m, k, k)
+    used = lens[np.arange(m)[None, :], codes[:-1], codes[1:]]
+    assert used.min() >= 1 and used.max() > 9 + 8, used.max()   # W1 + the second level
+    enc = codec.encode(ctx, tabs, torch.from_numpy(codes).cuda(), chunk_vectors=chunk)
+    dec = codec.decode(ctx, tabs, enc)
+    codec.decode_status(ctx)
+    assert np.array_equal(dec.cpu().numpy(), codes)
+
+
 @pytest.mark.parametrize("ctxm", [True, False])
 def test_full_size_roundtrip_sift1m(gpu, oracle, ctxm):
     """SIFT1M-shaped: assign (MFMA) -> hist -> codebooks -> encode -> decode; exact round

@@ -166,6 +166,42 @@ def test_gpu_tree_encode_vs_oracle_roundtrip(gpu, oracle, n, m, roots):
 
 
 @pytest.mark.gpu
+def test_gpu_tree_decode_long_codes(gpu):
+    """Tree decode through the long-code list.  One path (each row's parent is the row before
+    it), every part the same column, which alternates 0 and a symbol s in 1..24 that occurs
+    fib(s) times: the pair histogram of context 0 is Fibonacci, so its codes run past the
+    first table level (9 bits) and the second (8 more)."""
+    import torch
+    from pq_huffman_amd import codec
+    fib = [1, 1]
+    while len(fib) < 24:
+        fib.append(fib[-1] + fib[-2])
+    syms = np.repeat(np.arange(1, 25), fib)
+    np.random.default_rng(24).shuffle(syms)
+    col = np.zeros(2 * len(syms), np.uint8)
+    col[1::2] = syms
+    n, m = len(col), 8
+    codes = np.ascontiguousarray(np.repeat(col[:, None], m, axis=1))
+    counts = np.full(n, 2, np.int32)
+    counts[0] = counts[-1] = 1
+    v = np.arange(n)
+    targets = np.stack([v - 1, v + 1], axis=1).reshape(-1)[1:-1].astype(np.uint32)
+    enc = codec.tree_encode(gpu, torch.from_numpy(codes).cuda(), targets, counts)
+    rows = codes[enc.vertices]
+    pp, _, _ = codec.tree_ext_index(enc.num_children, enc.chunk_vectors)
+    child = np.flatnonzero(pp >= 0)
+    assert len(child) == n - 1
+    lens = enc.tables.codebooks().lengths().reshape(m, 256, 256)
+    used = lens[np.arange(m)[None, :], rows[pp[child]], rows[child]]
+    assert used.min() >= 1 and used.max() > 9 + 8, used.max()
+    for c in (16, 7):
+        e2 = enc if c == 16 else codec.tree_encode(gpu, torch.from_numpy(codes).cuda(), targets,
+                                                   counts, chunk_vectors=c)
+        dec = codec.tree_decode(gpu, e2).cpu().numpy()
+        np.testing.assert_array_equal(dec, rows)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("cut", [1, 4, 1000])
 def test_gpu_tree_decode_rejects_truncated_stream(gpu, cut):
     """A stream shorter than the encoder's sidecar says (a truncated huffman_indices.bin)
