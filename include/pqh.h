@@ -82,11 +82,13 @@ int pqh_ctx_sync(pqh_ctx_t* ctx);
  *   PQH_TUNE_HIST_BLOCK         its workgroup size, 256 or 1024 threads (PQH_HIST_BLOCK);
  *   PQH_TUNE_ENC_IMPL           the whole-stream encoder of pqh_encode_write*: 1 = tiled
  *                               (tiles in context scratch, scan, placement), 2 = one pass
- *                               with a decoupled look-back (PQH_ENC_IMPL=onepass).
+ *                               with a decoupled look-back (PQH_ENC_IMPL=onepass);
+ *   PQH_TUNE_SEARCH_GROUPS      workgroups per query batch of the ADC scan (pqh_search_*;
+ *                               default: the context's compute units over the batches).
  * A histogram that runs beside the assignment grid (on another stream) fits best at
  * split 4, 256 threads. */
 enum { PQH_TUNE_ASSIGN_WGS_PER_CU = 1, PQH_TUNE_HIST_SPLIT = 2, PQH_TUNE_HIST_BLOCK = 3,
-       PQH_TUNE_ENC_IMPL = 4 };
+       PQH_TUNE_ENC_IMPL = 4, PQH_TUNE_SEARCH_GROUPS = 5 };
 int pqh_ctx_set_tuning(pqh_ctx_t* ctx, int key, double value);
 const char* pqh_status_string(int status);
 const char* pqh_ctx_last_error(const pqh_ctx_t* ctx);
@@ -330,6 +332,51 @@ int pqh_fetch_vectors(pqh_ctx_t* ctx, const pqh_tables_t* t, const pqh_pq_t* pq,
                       int raw_first, int chunk_vectors, const unsigned long long* d_chunk_offsets,
                       const void* d_chunk_prev, const long long* d_ids, long long count,
                       float* d_out, long long ld_out);
+/* ---- search: asymmetric distance (ADC) top-k over a stream or over plain codes ---------
+ * A PQ store is searched with one table per query, lut[i][c] = the distance part of
+ * sub-vector i to centroid c; a row's distance is the sum of its m entries and the top_k
+ * smallest win.  pqh_search_stream decodes the stream chunk by chunk as pqh_decode does and
+ * scores every row where pqh_decode would store it: the codes are never written.  Its ids go
+ * straight into pqh_fetch_vectors for an exact re-rank.
+ * Device pointers, asynchronous on the context's stream.  A NULL context -- all a process
+ * without a GPU can have -- returns PQH_ERR_NO_DEVICE when no HIP device is visible and
+ * PQH_ERR_ARG otherwise; that check comes first, every other argument check after it.
+ * PQH_ERR_ARG: a null pointer, top_k < 1 or > PQH_SEARCH_MAX_K, chunk_vectors < 1, a
+ * negative count.  PQH_ERR_UNSUPPORTED: K > 256 (a K = 4096 table is 128 KB per query: no
+ * batch of them fits the LDS), m > 16, a chunk of more than ~90 KB of codes (C * m).
+ * Tree-mode streams are out of scope, as for random access.  nq == 0 launches nothing; n == 0
+ * fills the outputs with the padding.  The tables may hold any finite floats (negative ones,
+ * inner products); the result for NaN entries is unspecified.
+ * Scratch: 12 bytes * nq * top_k per workgroup of the scan grid, in the context workspace. */
+#define PQH_SEARCH_MAX_K 64
+
+/* lut[q][i][c] = sum_j (query[q][i*dsub+j] - cent[i][c][j])^2: fp32, j order, no contraction
+ * (the oracle arithmetic of pqh_pq_assign).  d_lut: device float [nq][m][K].  K <= 256.
+ * Query rows are ld_q >= m * dsub floats apart. */
+int pqh_adc_tables(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
+                   long long ld_q, float* d_lut);
+
+/* For each query q < nq: the top_k rows of the stream with the smallest
+ * dist(v) = ((lut[q][0][c_0] + lut[q][1][c_1]) + ...) + lut[q][m-1][c_{m-1}]
+ * (fp32, parts added left to right), ordered by (dist, row id) ascending -- fp32 `<` on the
+ * value, then on the id, so the result is unique; ids are row numbers in the stream plus
+ * id_base.  d_dist float [nq][top_k], d_ids int64 [nq][top_k]; when n < top_k the tail is
+ * (+inf, -1).  Stream, index and raw_first are pqh_decode's.
+ * Decode errors are pqh_decode_select's: an invalid code, a chunk offset or a symbol past
+ * stream_bytes * 8 bits make pqh_decode_status answer PQH_ERR_CORRUPT, and the rows of the
+ * failed chunk take no part in the result; a start past the stream is refused before
+ * anything is read, and nothing is read outside the stream. */
+int pqh_search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                      unsigned long long stream_bytes, long long n, int raw_first,
+                      int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                      const void* d_chunk_prev, const float* d_lut, long long nq, int top_k,
+                      long long id_base, float* d_dist, long long* d_ids);
+
+/* The same scan over plain row-major u8 codes [n][m]; k = the table width K. */
+int pqh_search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                     const float* d_lut, long long nq, int top_k, long long id_base,
+                     float* d_dist, long long* d_ids);
+
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by
  * the reference encoder) with a sequential table walk on the HOST copy of the stream
  * (index building only; the symbols themselves are decoded on the GPU). */

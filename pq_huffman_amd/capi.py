@@ -153,6 +153,9 @@ SIGNATURES = [
     ("pqh_decode_range", I, [P, P, P, ULL, LL, I, I, P, P, LL, LL, P]),
     ("pqh_fetch_vectors", I, [P, P, P, P, ULL, LL, I, I, P, P, P, LL, P, LL]),
     ("pqh_decode_files_range", I, [S, LL, LL, P, P]),
+    ("pqh_adc_tables", I, [P, P, P, LL, LL, P]),
+    ("pqh_search_stream", I, [P, P, P, ULL, LL, I, I, P, P, P, LL, I, LL, P, P]),
+    ("pqh_search_codes", I, [P, P, LL, I, I, P, LL, I, LL, P, P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

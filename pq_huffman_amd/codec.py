@@ -11,6 +11,7 @@ calls on device-resident data:
     build_codebooks      huffman_encoder.c:377-388 (huffman_codebook_[context_]encode_init)
     encode               huffman_encoder.c:413-428 (+ sidecar chunk index)
     decode               huffman_decoder.c:206-255
+    search               ADC top-k over the stream, fused into the decoder (no reference analogue)
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel.  Device buffers are torch tensors owned by the caller.
@@ -89,12 +90,13 @@ class Context:
         self.stream = stream
         check(lib().pqh_ctx_set_stream(self.ptr, ctypes.c_void_p(stream.cuda_stream)))
 
-    TUNE = {"assign_wgs_per_cu": 1, "hist_split": 2, "hist_block": 3, "enc_impl": 4}
+    TUNE = {"assign_wgs_per_cu": 1, "hist_split": 2, "hist_block": 3, "enc_impl": 4,
+            "search_groups": 5}
 
     def set_tuning(self, **kw) -> "Context":
         """launch shapes of this context's kernels (pqh_ctx_set_tuning; results never
-        change): assign_wgs_per_cu, hist_split, hist_block, enc_impl (1 tiled, 2 one-pass)
-        -- 0 restores the default"""
+        change): assign_wgs_per_cu, hist_split, hist_block, enc_impl (1 tiled, 2 one-pass),
+        search_groups (workgroups per query batch of the ADC scan) -- 0 restores the default"""
         for key, value in kw.items():
             check(lib().pqh_ctx_set_tuning(self.ptr, self.TUNE[key], float(value)),
                   f"pqh_ctx_set_tuning({key})")
@@ -599,6 +601,48 @@ def fetch(ctx: Context, tables: Tables, pq: PQ, enc: Encoded, ids, out=None):
     check(lib().pqh_fetch_vectors(ctx.ptr, tables.ptr, pq.ptr, *_index_args(enc), _ptr(ids),
                                   ids.numel(), _ptr(out), out.stride(0)), "pqh_fetch_vectors")
     return out
+
+
+def adc_tables(ctx: Context, pq: PQ, queries, out=None):
+    """the ADC tables of `queries` (device float32 (nq, >= m * dsub)): float32 (nq, m, K),
+    lut[q][i][c] = ||q_i - cent[i][c]||^2 in the assignment's arithmetic (pqh_adc_tables)."""
+    torch = _torch()
+    nq = queries.shape[0]
+    if out is None:
+        out = torch.empty((nq, pq.m, pq.k), dtype=torch.float32, device=queries.device)
+    check(lib().pqh_adc_tables(ctx.ptr, pq.ptr, _ptr(queries), nq, queries.stride(0), _ptr(out)),
+          "pqh_adc_tables")
+    return out
+
+
+def _search_out(lut, k, out):
+    torch = _torch()
+    if out is not None:
+        return out
+    nq = lut.shape[0]
+    return (torch.empty((nq, k), dtype=torch.float32, device=lut.device),
+            torch.empty((nq, k), dtype=torch.int64, device=lut.device))
+
+
+def search(ctx: Context, tables: Tables, enc: Encoded, lut, k: int, id_base: int = 0, out=None):
+    """(dist, ids), each (nq, k): per query table lut[q] (float32 (m, K)) the k rows of the
+    stream with the smallest summed entries, ascending by (dist, id), ids = stream rows +
+    id_base, padded with (+inf, -1); the stream is decoded and scored in one kernel, the
+    codes never written (pqh_search_stream).  Async; decode_status reports a corrupt stream.
+    out: a (dist, ids) pair to fill."""
+    dist, ids = _search_out(lut, k, out)
+    check(lib().pqh_search_stream(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut), lut.shape[0],
+                                  k, id_base, _ptr(dist), _ptr(ids)), "pqh_search_stream")
+    return dist, ids
+
+
+def search_codes(ctx: Context, codes, lut, k: int, id_base: int = 0, out=None):
+    """search() over plain uint8 codes (n, m) (pqh_search_codes)."""
+    dist, ids = _search_out(lut, k, out)
+    check(lib().pqh_search_codes(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1],
+                                 lut.shape[2], _ptr(lut), lut.shape[0], k, id_base, _ptr(dist),
+                                 _ptr(ids)), "pqh_search_codes")
+    return dist, ids
 
 
 def encode_status(ctx: Context) -> None:

@@ -231,6 +231,10 @@ int pqh_ctx_set_tuning(pqh_ctx_t* ctx, int key, double value) {
             ctx->tune_enc_impl = v;
             return PQH_OK;
         }
+        case PQH_TUNE_SEARCH_GROUPS:
+            if (value > 65535.0) return PQH_ERR_ARG;
+            ctx->tune_search_groups = (int)value;
+            return PQH_OK;
         default:
             return PQH_ERR_ARG;
     }

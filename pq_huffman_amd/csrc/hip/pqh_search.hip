@@ -1,0 +1,633 @@
+// pqh_search.hip -- asymmetric distance (ADC) search of a compressed stream: the decoder of
+// pqh_decode.hip with a scoring phase where its store was.
+//
+//  adc_lut     lut[q][i][c] = ||q_i - cent[i][c]||^2, one thread per entry (the oracle
+//              arithmetic of pqh_pq_assign: fp32, j order, no contraction).
+//  adc_scan    one lane per chunk, 64 chunks per wave and step: the chunks' stream window and
+//              their decoded rows staged in the wave's LDS (walk_packed / walk_parts of
+//              pqh_decode_dev.h), then every row scored against a batch of QB query tables
+//              held in LDS with the query innermost, and offered to QB per-wave top-k lists
+//              (one entry per lane, ascending by (dist, id)), merged per workgroup at the
+//              end.  The codes never reach memory.
+//              SRC = 1 loads plain u8 rows into the same stage instead of decoding them.
+//  adc_merge   one workgroup per query: every scan workgroup's list through the same list code.
+//
+// dist(v) = ((lut[0][c_0] + lut[1][c_1]) + ...) + lut[m-1][c_{m-1}] in fp32, the order total
+// (dist, then row id), so the result does not depend on the grid.
+#include <algorithm>
+#include <cmath>
+#include <type_traits>
+
+#include "pqh_internal.h"
+#include "pqh_decode_dev.h"
+
+namespace {
+
+constexpr int kScanWavesMax = 16;          // waves per workgroup (threadIdx.y; threadIdx.x = lane)
+constexpr int kLdsBytes = 160 * 1024;
+constexpr int kCodesRowsPerLane = 4;       // SRC = 1: a wave stages 64 * 4 rows per step
+
+__global__ void __launch_bounds__(256)
+adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
+        const float* __restrict__ cent, int m, int k, int dsub, float* __restrict__ lut) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long per = (long long)m * k;
+    if (idx >= nq * per) return;
+    const long long q = idx / per;
+    const int e = (int)(idx - q * per);   // i * k + c
+    const float* x = queries + q * ld_q + (long long)(e / k) * dsub;
+    const float* c = cent + (long long)e * dsub;
+    float acc = 0.f;
+    for (int j = 0; j < dsub; ++j) {
+        const float t = x[j] - c[j];
+        acc = acc + t * t;
+    }
+    lut[idx] = acc;
+}
+
+// ------------------------------------------------------------------- the top-k list
+// A wave's list: 64 entries, one per lane, ascending by (d, id); unused entries are
+// (+inf, -1), which every finite candidate precedes.  Only the first top_k lanes are the
+// result; the threshold a candidate has to beat is the entry of lane top_k - 1.
+struct TopK {
+    float d;
+    long long id;
+};
+
+__device__ __forceinline__ bool lex_lt(float a, long long ia, float b, long long ib) {
+    return (a < b) | ((a == b) & (ia < ib));   // (no short circuit: selects, not branches)
+}
+__device__ __forceinline__ float lane_f(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ __forceinline__ long long lane_ll(long long v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), l);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ int wave_shr1(int v) {   // lane i takes lane i - 1 (lane 0 keeps v)
+    return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xF, 0xF, false);
+}
+
+// the wave-uniform candidate (cd, cid) into its place: its position is the number of entries
+// before it; the entries from there on move one lane up (the last one falls off)
+__device__ __forceinline__ void list_insert(TopK& e, float cd, long long cid) {
+    const int lane = threadIdx.x;
+    const int pos = __popcll(__ballot(lex_lt(e.d, e.id, cd, cid)));
+    const float pd = __int_as_float(wave_shr1(__float_as_int(e.d)));
+    const uint32_t plo = (uint32_t)wave_shr1((int)(uint32_t)e.id);
+    const uint32_t phi = (uint32_t)wave_shr1((int)(uint32_t)((unsigned long long)e.id >> 32));
+    const long long pid = (long long)(((unsigned long long)phi << 32) | plo);
+    e.d = lane > pos ? pd : lane == pos ? cd : e.d;
+    e.id = lane > pos ? pid : lane == pos ? cid : e.id;
+}
+
+// ---- many candidates at once: a bitonic network over the wave, one key per lane
+// the lane keeps the smaller (take_min) or the larger of its key and lane ^ j's
+__device__ __forceinline__ void key_exchange(TopK& x, int j, bool take_min) {
+    const TopK p{__shfl_xor(x.d, j), __shfl_xor(x.id, j)};
+    const bool take = take_min == lex_lt(p.d, p.id, x.d, x.id);
+    x.d = take ? p.d : x.d;
+    x.id = take ? p.id : x.id;
+}
+
+// The 64 smallest of the list and the 64 keys c, sorted, into the list.  c is sorted ascending
+// first unless it already is (SORTED); reversed, its lane-wise minimum with the list holds the
+// 64 smallest of both as a bitonic sequence, which six exchange steps sort.  Lanes without a
+// candidate carry (+inf, max id), which no list entry follows.
+template <bool SORTED>
+__device__ __forceinline__ void list_merge(TopK& e, TopK c) {
+    const int lane = threadIdx.x;
+    if constexpr (!SORTED) {
+#pragma unroll
+        for (int k = 2; k <= 64; k <<= 1)
+#pragma unroll
+            for (int j = k >> 1; j > 0; j >>= 1)
+                key_exchange(c, j, ((lane & j) == 0) == ((lane & k) == 0));
+    }
+    const TopK r{__shfl(c.d, 63 - lane), __shfl(c.id, 63 - lane)};
+    const bool take = lex_lt(r.d, r.id, e.d, e.id);
+    e.d = take ? r.d : e.d;
+    e.id = take ? r.id : e.id;
+#pragma unroll
+    for (int j = 32; j > 0; j >>= 1) key_exchange(e, j, (lane & j) == 0);
+}
+
+// Every lane offers one candidate (d, id) (valid: it takes part).  The ones before the
+// threshold are inserted one by one, lowest lane first, the threshold moving with every insert
+// so that the rest are filtered again; more than kSerialMax of them go through list_merge
+// instead (an insert is a chain of ~50 dependent instructions, the network ~28 exchange steps
+// whatever the count).  SORTED: the candidates ascend with the lane.  Called by the whole wave.
+constexpr int kSerialMax = 6;
+template <bool SORTED>
+__device__ __forceinline__ void list_offer(TopK& e, float d, long long id, bool valid, int kth) {
+    float td = lane_f(e.d, kth);
+    long long tid = lane_ll(e.id, kth);
+    const bool pass = valid && lex_lt(d, id, td, tid);
+    unsigned long long mask = __ballot(pass);
+    if (!mask) return;
+    if (__popcll(mask) > kSerialMax) {
+        list_merge<SORTED>(e, pass ? TopK{d, id} : TopK{INFINITY, 0x7FFFFFFFFFFFFFFFll});
+        return;
+    }
+    while (mask) {
+        const int l = __builtin_ctzll(mask);
+        list_insert(e, lane_f(d, l), lane_ll(id, l));
+        td = lane_f(e.d, kth);
+        tid = lane_ll(e.id, kth);
+        mask &= mask - 1;
+        mask &= __ballot(valid && lex_lt(d, id, td, tid));
+    }
+}
+
+// LDS written by some lanes of this wave and read by others: all of it done before any lane
+// goes on (the stage and the window are the wave's own, so no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ------------------------------------------------------------------- the scan
+struct ScanArgs {
+    const uint32_t* words;      // SRC = 0: the stream
+    long long nwords;
+    const unsigned long long* chunk_off;
+    const void* chunk_prev;
+    DecTabs T;
+    int raw_first;
+    const unsigned char* codes; // SRC = 1: rows [n][m]
+    long long n;
+    int m, k;
+    int C;                      // rows per lane and step (SRC = 0: the chunk size)
+    int L;                      // lanes (chunks) per wave and step, 64 unless a chunk's rows
+                                // are too many for the stage
+    long long steps;            // ceil(chunks / L)
+    int stage_bytes, win_words; // per wave
+    const float* lut;           // [nq][m][k]
+    long long nq;
+    int top_k;
+    float* part_d;              // [nq][groups][top_k]: one list per workgroup and query
+    long long* part_id;
+    unsigned long long* err;
+};
+
+template <int SRC, int NW, bool CTX, int QB>
+__global__ void __launch_bounds__(64 * kScanWavesMax)
+adc_scan(const ScanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int lane = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    const int waves = (int)blockDim.y;
+    const int m = NW ? 8 * NW : a.m;
+    const int k = a.k;
+    const int C = a.C;
+    const int mk = m * k;
+    float* lut_lds = reinterpret_cast<float*>(lds);   // [m][k][QB]
+    const int per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
+    unsigned char* stage = reinterpret_cast<unsigned char*>(lds) + (size_t)mk * QB * 4 +
+                           (size_t)wave * per_wave;
+    uint32_t* win = reinterpret_cast<uint32_t*>(stage + a.stage_bytes);
+
+    // the batch's tables, the query innermost: one 16-byte read is four queries' entries
+    const long long q0 = (long long)blockIdx.x * QB;
+    for (int e = wave * 64 + lane; e < mk; e += waves * 64) {
+        float v[QB];
+#pragma unroll
+        for (int qq = 0; qq < QB; ++qq) v[qq] = q0 + qq < a.nq ? a.lut[(q0 + qq) * mk + e] : 0.f;
+#pragma unroll
+        for (int u = 0; u < QB / 4; ++u)
+            reinterpret_cast<float4*>(lut_lds + (size_t)e * QB)[u] =
+                make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+    }
+    lds_barrier();
+
+    TopK list[QB];
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq) list[qq] = TopK{INFINITY, -1ll};
+    const int kth = a.top_k - 1;
+
+    const long long chunks = (a.n + C - 1) / C;
+    const unsigned long long nbits = (unsigned long long)a.nwords * 32;
+    // this workgroup's span of steps; its waves take them in turn
+    const long long g_lo = (long long)blockIdx.y * a.steps / gridDim.y;
+    const long long g_hi = ((long long)blockIdx.y + 1) * a.steps / gridDim.y;
+#pragma unroll 1
+    for (long long g = g_lo + wave; g < g_hi; g += waves) {
+        const long long j0 = g * a.L;
+        const long long jn = min(chunks - j0, (long long)a.L);
+        const long long row0 = j0 * C;
+        const int nrows = (int)(min(a.n, (j0 + a.L) * C) - row0);
+        unsigned long long dead = 0;   // lanes whose chunk failed
+        if constexpr (SRC == 0) {
+            bool use_win = false;
+            StreamWin sw{0, 0, false};
+            if (a.win_words > 0) {   // (then L = 64: the window is that of 64 chunks)
+                const unsigned long long b_lo = a.chunk_off[j0];
+                const unsigned long long b_hi = j0 + 64 < chunks ? a.chunk_off[j0 + 64] : nbits;
+                // (an index that does not ascend or leaves the stream: no window, every
+                // lane's own offset is then checked by SelRd)
+                if (b_lo <= nbits && b_hi >= b_lo) {
+                    sw = stage_window<4, true>(a.words, a.nwords, a.chunk_off, j0, chunks, win,
+                                               a.win_words);
+                    use_win = sw.in_lds;
+                }
+            }
+            wave_lds_sync();
+            bool ok = true;
+            if (lane < jn) {
+                const long long j = j0 + lane;
+                const unsigned long long off = a.chunk_off[j];
+                const int cnt = (int)min((long long)C, a.n - j * C);
+                const bool raw = CTX && j == 0 && a.raw_first;
+                auto walk = [&](auto& br) -> bool {
+                    if constexpr (NW > 0) {
+                        unsigned long long* st =
+                            reinterpret_cast<unsigned long long*>(stage) + (long long)lane * C * NW;
+                        unsigned long long prev[NW];
+#pragma unroll
+                        for (int w = 0; w < NW; ++w) prev[w] = 0;
+                        if (CTX && !raw) {
+#pragma unroll
+                            for (int w = 0; w < NW; ++w)
+                                prev[w] = static_cast<const unsigned long long*>(a.chunk_prev)[j * NW + w];
+                        }
+                        return walk_packed<CTX, NW, 8>(br, a.T, raw, cnt, prev,
+                                                       [&](int s, int w, unsigned long long row) {
+                                                           st[s * NW + w] = row;
+                                                       });
+                    } else {
+                        // the running row is the stage slot being decoded: it starts as a
+                        // copy of the row before it
+                        unsigned char* st = stage + (long long)lane * C * m;
+                        for (int i = 0; i < m; ++i)
+                            st[i] = (CTX && !raw)
+                                        ? static_cast<const unsigned char*>(a.chunk_prev)[j * m + i]
+                                        : (unsigned char)0;
+                        int cur = 0;
+                        return walk_parts<0>(
+                            br, a.T, m, CTX, raw, cnt,
+                            [&](int i) -> unsigned char& { return st[cur * m + i]; },
+                            [&](int s) {
+                                if (s + 1 < cnt)
+                                    for (int i = 0; i < m; ++i) st[(s + 1) * m + i] = st[s * m + i];
+                                cur = s + 1;
+                            });
+                    }
+                };
+                ok = off <= nbits;   // a start past the stream is refused before anything is read
+                if (ok && use_win) {
+                    const unsigned long long w_bits = (unsigned long long)sw.w_lo * 32;
+                    ok = off >= w_bits && off <= w_bits + (unsigned long long)sw.nw * 32;
+                    if (ok) {
+                        PosRd br;
+                        br.init(win, (uint32_t)(sw.nw + 3), off - w_bits);
+                        ok = walk(br) && w_bits + br.bit() <= nbits;
+                    }
+                } else if (ok) {
+                    SelRd rd;
+                    ok = rd.init(a.words, a.nwords, off);
+                    if (ok) ok = walk(rd.br) && rd.pos() <= nbits;
+                }
+            }
+            dead = __ballot(lane < jn && !ok);
+            if (dead && lane == 0) atomicOr(a.err, 1ull);
+        } else {
+            const long long nbytes = (long long)nrows * m;
+            const unsigned char* src = a.codes + row0 * m;
+            long long done = 0;
+            if (!(reinterpret_cast<uintptr_t>(src) & 3u)) {
+                done = nbytes & ~3ll;
+                for (long long q = lane; q < done / 4; q += 64)
+                    reinterpret_cast<uint32_t*>(stage)[q] =
+                        __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src) + q);
+            }
+            for (long long q = done + lane; q < nbytes; q += 64) stage[q] = src[q];
+        }
+        wave_lds_sync();
+
+        // the stage holds the wave's rows row0 ... row0 + nrows - 1 in order: lane scores
+        // rows lane, lane + 64, ...
+#pragma unroll 1
+        for (int base = 0; base < nrows; base += 64) {
+            const int r = base + lane;
+            bool valid = r < nrows;
+            if (dead && valid) valid = !((dead >> (r / C)) & 1ull);
+            const unsigned char* row = stage + (long long)(r < nrows ? r : 0) * m;
+            float sum[QB];
+            auto add = [&](int i, unsigned c) {
+                // (a failed chunk's slots hold anything: keep the read inside the table)
+                const float4* e = reinterpret_cast<const float4*>(
+                    lut_lds + (size_t)(i * k + (int)min(c, (unsigned)(k - 1))) * QB);
+#pragma unroll
+                for (int u = 0; u < QB / 4; ++u) {
+                    const float4 v = e[u];
+                    if (i == 0) {
+                        sum[4 * u] = v.x, sum[4 * u + 1] = v.y, sum[4 * u + 2] = v.z, sum[4 * u + 3] = v.w;
+                    } else {
+                        sum[4 * u] = sum[4 * u] + v.x;
+                        sum[4 * u + 1] = sum[4 * u + 1] + v.y;
+                        sum[4 * u + 2] = sum[4 * u + 2] + v.z;
+                        sum[4 * u + 3] = sum[4 * u + 3] + v.w;
+                    }
+                }
+            };
+            if constexpr (NW > 0) {
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    const unsigned long long word = reinterpret_cast<const unsigned long long*>(row)[w];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) add(w * 8 + i, (unsigned)(word >> (8 * i)) & 255u);
+                }
+            } else {
+                add(0, row[0]);
+#pragma unroll 1
+                for (int i = 1; i < m; ++i) add(i, row[i]);
+            }
+            const long long id = row0 + r;
+#pragma unroll
+            for (int qq = 0; qq < QB; ++qq)
+                if (q0 + qq < a.nq) list_offer<false>(list[qq], sum[qq], id, valid, kth);
+        }
+        wave_lds_sync();   // the next step's staging overwrites what was just read
+    }
+
+    // The workgroup's lists into one per query: the tables and the stages are done with, so
+    // every wave leaves its lists in LDS and wave w merges those of queries w, w + waves, ...
+    lds_barrier();
+    float* ex_d = reinterpret_cast<float*>(lds);   // [waves][QB][64]
+    long long* ex_id = reinterpret_cast<long long*>(lds + (size_t)waves * QB * 64 * 4);
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq) {
+        ex_d[(wave * QB + qq) * 64 + lane] = list[qq].d;
+        ex_id[(wave * QB + qq) * 64 + lane] = list[qq].id;
+    }
+    lds_barrier();
+#pragma unroll 1
+    for (int qq = wave; qq < QB && q0 + qq < a.nq; qq += waves) {
+        TopK e{INFINITY, -1ll};
+#pragma unroll 1
+        for (int s = 0; s < waves; ++s) {
+            const float d = ex_d[(s * QB + qq) * 64 + lane];
+            const long long id = ex_id[(s * QB + qq) * 64 + lane];
+            list_offer<true>(e, d, id, id >= 0, kth);
+        }
+        if (lane < a.top_k) {
+            const long long o = ((q0 + qq) * gridDim.y + blockIdx.y) * a.top_k + lane;
+            a.part_d[o] = e.d;
+            a.part_id[o] = e.id;
+        }
+    }
+}
+
+// One workgroup of kMergeWaves waves per query: each wave takes its share of the scan's lists
+// through the same list code (kMergeAhead loads in flight per lane), wave 0 then the other waves'; the
+// result padded with (+inf, -1) and the ids moved by id_base.  lists = 0: the padding alone.
+constexpr int kMergeWaves = 16;
+constexpr int kMergeAhead = 4;
+__global__ void __launch_bounds__(64 * kMergeWaves)
+adc_merge(const float* __restrict__ part_d, const long long* __restrict__ part_id, long long lists,
+          int top_k, long long id_base, float* __restrict__ dist, long long* __restrict__ ids) {
+    __shared__ float xd[(kMergeWaves - 1) * 64];
+    __shared__ long long xid[(kMergeWaves - 1) * 64];
+    const int lane = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    const long long q = blockIdx.x;
+    const long long total = lists * top_k;
+    const int kth = top_k - 1;
+    TopK e{INFINITY, -1ll};
+#pragma unroll 1
+    for (long long base = (long long)wave * 64 * kMergeAhead; base < total;
+         base += 64 * kMergeAhead * kMergeWaves) {
+        float d[kMergeAhead];
+        long long id[kMergeAhead];
+#pragma unroll
+        for (int u = 0; u < kMergeAhead; ++u) {
+            const long long idx = base + u * 64 + lane;
+            d[u] = idx < total ? part_d[q * total + idx] : INFINITY;
+            id[u] = idx < total ? part_id[q * total + idx] : -1ll;
+        }
+#pragma unroll
+        for (int u = 0; u < kMergeAhead; ++u) {   // (64 entries are one sorted list when top_k = 64)
+            if (top_k == 64)
+                list_offer<true>(e, d[u], id[u], id[u] >= 0, kth);
+            else
+                list_offer<false>(e, d[u], id[u], id[u] >= 0, kth);
+        }
+    }
+    if (wave > 0) {
+        xd[(wave - 1) * 64 + lane] = e.d;
+        xid[(wave - 1) * 64 + lane] = e.id;
+    }
+    lds_barrier();
+    if (wave == 0) {
+#pragma unroll 1
+        for (int s = 0; s < kMergeWaves - 1; ++s) {
+            const long long id = xid[s * 64 + lane];
+            list_offer<true>(e, xd[s * 64 + lane], id, id >= 0, kth);
+        }
+        if (lane < top_k) {
+            dist[q * top_k + lane] = e.d;
+            ids[q * top_k + lane] = e.id < 0 ? -1ll : e.id + id_base;
+        }
+    }
+}
+
+// ------------------------------------------------------------------- host side
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+int floor_pow2(long long v) {
+    int p = 1;
+    while (2ll * p <= v) p *= 2;
+    return p;
+}
+
+// a NULL context is all a process without a GPU can have (pqh_ctx_create fails there)
+int no_ctx_status() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        return PQH_ERR_NO_DEVICE;
+    }
+    return PQH_ERR_ARG;
+}
+
+int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long long lists,
+                 long long nq, int top_k, long long id_base, float* d_dist, long long* d_ids) {
+    hipLaunchKernelGGL(adc_merge, dim3((unsigned)nq), dim3(64, kMergeWaves), 0, ctx->stream, pd,
+                       pid, lists, top_k, id_base, d_dist, d_ids);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+// the scan and the merge; a.C, a.n, a.m, a.k and the source are set by the caller, nw = the
+// row's u64 words (0: per part)
+int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long id_base,
+                float* d_dist, long long* d_ids) {
+    if (a.nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    const int m = a.m, k = a.k;
+    // the batch's tables: at most 64 KB; 16-part rows keep to four queries (eight running
+    // sums beside sixteen unrolled parts spill registers)
+    const int qb = (m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
+    const long long lut_bytes = (long long)m * k * qb * 4;
+    const long long budget = kLdsBytes - lut_bytes;
+    const long long chunks = (a.n + a.C - 1) / a.C;
+    // a wave's stage: the rows of 64 chunks, or of as many as fit
+    const long long row_bytes = (long long)a.C * m;
+    a.L = 64;
+    if (((64 * row_bytes + 15) & ~15ll) > budget) a.L = (int)((budget - 16) / row_bytes);
+    if (a.L < 1) return PQH_ERR_UNSUPPORTED;   // (a chunk of more than ~96 KB of codes)
+    a.stage_bytes = (int)((a.L * row_bytes + 15) & ~15ll);
+    // the stream window as pqh_decode's row kernels size it (a longer span is read from
+    // global memory)
+    a.win_words = 0;
+    if (src == 0 && a.L == 64) {
+        const long long span_words = (64ll * a.C * m * 12 + 31) / 32 + 8;
+        const long long ww = std::min<long long>(4096 - 1024 * (nw == 2 ? 1 : 0),
+                                                 std::max<long long>(256, span_words));
+        a.win_words = (int)((ww + 3) & ~3ll);
+        if (a.stage_bytes + (a.win_words + 4) * 4 > budget) a.win_words = 0;
+    }
+    const long long per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
+    const int fit = floor_pow2(std::min<long long>(kScanWavesMax, budget / per_wave));
+    a.steps = (chunks + a.L - 1) / a.L;
+    const long long batches = (a.nq + qb - 1) / qb;
+    // one workgroup per compute unit over all query batches (a workgroup's tables take most
+    // of a compute unit's LDS), each wave with at least two steps where there are that many
+    long long groups = ctx->tune_search_groups > 0 ? ctx->tune_search_groups
+                                                   : std::max<long long>(1, ctx->num_cus / batches);
+    groups = std::min<long long>(std::min<long long>(groups, a.steps), 65535);
+    const int waves = std::min(fit, floor_pow2((a.steps + 2 * groups - 1) / (2 * groups)));
+    const long long lists = groups;   // (a workgroup merges its waves' lists)
+    const size_t entries = (size_t)a.nq * lists * a.top_k;
+    int rc = pqh_ensure_ws(ctx, entries * 12 + 16);
+    if (rc) return rc;
+    a.part_id = static_cast<long long*>(ctx->ws);
+    a.part_d = reinterpret_cast<float*>(a.part_id + entries);
+    a.err = ctx->d_diag + 1;
+    // (the end of the kernel exchanges the waves' lists, 12 bytes an entry, through the same LDS)
+    const size_t lds = std::max<size_t>((size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
+                                        (size_t)waves * qb * 64 * 12);
+    auto launch = [&](auto s, auto w, auto c, auto q) -> int {
+        auto* fn = adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
+                            decltype(q)::value>;
+        if (lds > 64 * 1024)
+            PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(fn, dim3((unsigned)batches, (unsigned)groups), dim3(64, waves), lds,
+                           ctx->stream, a);
+        return PQH_OK;
+    };
+    auto with_qb = [&](auto s, auto w, auto c) -> int {
+        if constexpr (decltype(w)::value != 2)
+            if (qb == 8) return launch(s, w, c, Int<8>());
+        return launch(s, w, c, Int<4>());
+    };
+    auto with_nw = [&](auto s, auto c) -> int {
+        return nw == 1 ? with_qb(s, Int<1>(), c) : nw == 2 ? with_qb(s, Int<2>(), c)
+                                                           : with_qb(s, Int<0>(), c);
+    };
+    if (src == 1)
+        rc = with_nw(Int<1>(), std::false_type());
+    else
+        rc = cx ? with_nw(Int<0>(), std::true_type()) : with_nw(Int<0>(), std::false_type());
+    if (rc) return rc;
+    PQH_LAUNCH_CHECK(ctx);
+    return merge_launch(ctx, a.part_d, a.part_id, lists, a.nq, a.top_k, id_base, d_dist, d_ids);
+}
+
+// the checks the two scans share; *run = false: nothing (more) to launch
+int search_check(pqh_ctx_t* ctx, bool have_src, long long n, const float* d_lut, long long nq,
+                 int top_k, long long id_base, float* d_dist, long long* d_ids, bool* run) {
+    *run = false;
+    if (n < 0 || nq < 0 || top_k < 1 || top_k > PQH_SEARCH_MAX_K) return PQH_ERR_ARG;
+    if (nq > 0 && (!d_lut || !d_dist || !d_ids || (n > 0 && !have_src))) return PQH_ERR_ARG;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (nq == 0) return PQH_OK;
+    if (nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    if (n == 0) return merge_launch(ctx, nullptr, nullptr, 0, nq, top_k, id_base, d_dist, d_ids);
+    *run = true;
+    return PQH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pqh_adc_tables(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
+                   long long ld_q, float* d_lut) {
+    if (!ctx) return no_ctx_status();
+    int m = 0, k = 0, dsub = 0;
+    const float* d_cent = nullptr;
+    if (pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || nq < 0 || ld_q < (long long)m * dsub ||
+        (nq > 0 && (!d_queries || !d_lut)))
+        return PQH_ERR_ARG;
+    if (k > 256) return PQH_ERR_UNSUPPORTED;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (nq == 0) return PQH_OK;
+    const long long blocks = (nq * m * k + 255) / 256;
+    if (blocks > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(adc_lut, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_queries, nq,
+                       ld_q, d_cent, m, k, dsub, d_lut);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int pqh_search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                      unsigned long long stream_bytes, long long n, int raw_first,
+                      int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                      const void* d_chunk_prev, const float* d_lut, long long nq, int top_k,
+                      long long id_base, float* d_dist, long long* d_ids) {
+    if (!ctx) return no_ctx_status();
+    if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
+    if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
+    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
+    if (t->k > 256 || t->m > 16) return PQH_ERR_UNSUPPORTED;
+    bool run = false;
+    int rc = search_check(ctx, d_stream != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
+    if (rc || !run) return rc;
+    if (stream_bytes / 4 >= (1ull << 58)) return PQH_ERR_UNSUPPORTED;
+    ScanArgs a{};
+    a.words = reinterpret_cast<const uint32_t*>(d_stream);
+    a.nwords = (long long)(stream_bytes / 4);
+    a.chunk_off = d_chunk_offsets;
+    a.chunk_prev = d_chunk_prev;
+    a.T = dec_tabs(t, 0);
+    a.raw_first = raw_first;
+    a.n = n;
+    a.m = t->m;
+    a.k = t->k;
+    a.C = chunk_vectors;
+    a.lut = d_lut;
+    a.nq = nq;
+    a.top_k = top_k;
+    // rows of whole u64 words with the chunk contexts readable as such: the packed walk
+    const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
+    return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, id_base, d_dist, d_ids);
+}
+
+int pqh_search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                     const float* d_lut, long long nq, int top_k, long long id_base,
+                     float* d_dist, long long* d_ids) {
+    if (!ctx) return no_ctx_status();
+    if (m < 1 || k < 1) return PQH_ERR_ARG;
+    if (k > 256 || m > 16) return PQH_ERR_UNSUPPORTED;
+    bool run = false;
+    int rc = search_check(ctx, d_codes != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
+    if (rc || !run) return rc;
+    ScanArgs a{};
+    a.codes = static_cast<const unsigned char*>(d_codes);
+    a.n = n;
+    a.m = m;
+    a.k = k;
+    a.C = kCodesRowsPerLane;
+    a.lut = d_lut;
+    a.nq = nq;
+    a.top_k = top_k;
+    return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids);
+}
+
+}  // extern "C"
