@@ -377,6 +377,45 @@ int pqh_search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, in
                      const float* d_lut, long long nq, int top_k, long long id_base,
                      float* d_dist, long long* d_ids);
 
+/* The probe search: the same top_k, but query q looks only at its own row ranges, the way an
+ * inverted file is searched -- the rows stored list by list and a query probing the few lists
+ * nearest to it.  The probe list is in CSR form, all of it device data (a coarse quantizer on
+ * the GPU hands it over without a host round trip): query q scans the ranges
+ * d_range_ptr[q] ... d_range_ptr[q + 1] - 1, and range r is the rows
+ * [d_ranges[2r], d_ranges[2r] + d_ranges[2r + 1]) of the stream.  d_range_ptr int64 [nq + 1],
+ * d_ranges int64 [nr][2].  Arithmetic, order, padding and id_base are pqh_search_stream's, and
+ * the result does not depend on the grid.
+ * A range need not start or end on a chunk boundary: a chunk that is cut is decoded from its
+ * start (chunk 0 with its raw first row) as far as the range goes, and only its rows inside
+ * the range are scored.  A chunk with no row in any range of a query is neither read nor
+ * decoded for that query, so the sound part of a damaged stream can be searched without
+ * PQH_ERR_CORRUPT; the decode errors are pqh_search_stream's for the chunks that are walked.
+ * The ranges of a query may overlap: a row is offered once for every range that holds it and
+ * may appear that many times in the result (no dedup).  count == 0 is an empty range, a query
+ * without ranges gets the padding.
+ * Bad values are reported as pqh_decode_select reports a bad id, by PQH_ERR_ARG from
+ * pqh_decode_status (PQH_ERR_CORRUPT takes precedence): a range with first < 0, count < 0,
+ * first > n or count > n - first is skipped as a whole; a query whose
+ * [d_range_ptr[q], d_range_ptr[q + 1]) is reversed or leaves [0, nr] scans nothing.  Every
+ * other range and query gives its exact result.
+ * PQH_ERR_ARG at once: the cases of pqh_search_stream, nr < 0, a null d_range_ptr when
+ * nq > 0, a null d_ranges when nq > 0 and nr > 0.  nq == 0 launches nothing; n == 0 or
+ * nr == 0 fills the outputs with the padding.
+ * Scratch: 12 bytes * nq * top_k per workgroup of the scan grid and 8 * (nr + 1) bytes. */
+int pqh_search_stream_ranges(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                             unsigned long long stream_bytes, long long n, int raw_first,
+                             int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                             const void* d_chunk_prev, const float* d_lut, long long nq,
+                             const long long* d_range_ptr /* [nq + 1] */,
+                             const long long* d_ranges /* [nr][2] */, long long nr, int top_k,
+                             long long id_base, float* d_dist, long long* d_ids);
+
+/* The same over plain row-major u8 codes [n][m]. */
+int pqh_search_codes_ranges(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                            const float* d_lut, long long nq, const long long* d_range_ptr,
+                            const long long* d_ranges, long long nr, int top_k, long long id_base,
+                            float* d_dist, long long* d_ids);
+
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by
  * the reference encoder) with a sequential table walk on the HOST copy of the stream
  * (index building only; the symbols themselves are decoded on the GPU). */

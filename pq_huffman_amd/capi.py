@@ -156,6 +156,8 @@ SIGNATURES = [
     ("pqh_adc_tables", I, [P, P, P, LL, LL, P]),
     ("pqh_search_stream", I, [P, P, P, ULL, LL, I, I, P, P, P, LL, I, LL, P, P]),
     ("pqh_search_codes", I, [P, P, LL, I, I, P, LL, I, LL, P, P]),
+    ("pqh_search_stream_ranges", I, [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, LL, P, P]),
+    ("pqh_search_codes_ranges", I, [P, P, LL, I, I, P, LL, P, P, LL, I, LL, P, P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

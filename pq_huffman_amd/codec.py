@@ -12,9 +12,12 @@ calls on device-resident data:
     encode               huffman_encoder.c:413-428 (+ sidecar chunk index)
     decode               huffman_decoder.c:206-255
     search               ADC top-k over the stream, fused into the decoder (no reference analogue)
+    search_ranges        the same over per-query row ranges: the probe search of an inverted file
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
-computation is a libpqh kernel.  Device buffers are torch tensors owned by the caller.
+computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
+(a sort and gathers of int64 in plain torch).  Device buffers are torch tensors owned by the
+caller.
 """
 from __future__ import annotations
 
@@ -643,6 +646,63 @@ def search_codes(ctx: Context, codes, lut, k: int, id_base: int = 0, out=None):
                                  lut.shape[2], _ptr(lut), lut.shape[0], k, id_base, _ptr(dist),
                                  _ptr(ids)), "pqh_search_codes")
     return dist, ids
+
+
+def search_ranges(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ranges, k: int,
+                  id_base: int = 0, out=None):
+    """search() of per-query row ranges, the way an inverted file is probed: query q scores
+    only the rows [ranges[r, 0], ranges[r, 0] + ranges[r, 1]) for r in
+    [range_ptr[q], range_ptr[q + 1]), and only the chunks under them are decoded
+    (pqh_search_stream_ranges).  range_ptr: device int64 (nq + 1,); ranges: device int64
+    (nr, 2).  Ranges may cut chunks and may overlap (a row is then offered once per range).
+    Async; decode_status reports a corrupt chunk that was walked (PQH_ERR_CORRUPT) or a bad
+    range or range_ptr value (PQH_ERR_ARG, the range or query skipped)."""
+    dist, ids = _search_out(lut, k, out)
+    check(lib().pqh_search_stream_ranges(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut),
+                                         lut.shape[0], _ptr(range_ptr), _ptr(ranges),
+                                         ranges.shape[0], k, id_base, _ptr(dist), _ptr(ids)),
+          "pqh_search_stream_ranges")
+    return dist, ids
+
+
+def search_codes_ranges(ctx: Context, codes, lut, range_ptr, ranges, k: int, id_base: int = 0,
+                        out=None):
+    """search_ranges() over plain uint8 codes (n, m) (pqh_search_codes_ranges)."""
+    dist, ids = _search_out(lut, k, out)
+    check(lib().pqh_search_codes_ranges(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1],
+                                        lut.shape[2], _ptr(lut), lut.shape[0], _ptr(range_ptr),
+                                        _ptr(ranges), ranges.shape[0], k, id_base, _ptr(dist),
+                                        _ptr(ids)), "pqh_search_codes_ranges")
+    return dist, ids
+
+
+def ivf_layout(list_ids, nlist: int):
+    """(perm, offsets) for storing rows list by list: perm is the stable order of the rows by
+    list id (stream row s holds original row perm[s]), offsets int64 (nlist + 1,) with list l
+    at stream rows [offsets[l], offsets[l + 1]).  list_ids: int64 (n,) in [0, nlist).  Plain
+    torch on the tensor's device, no sync."""
+    torch = _torch()
+    by_list, perm = torch.sort(list_ids, stable=True)
+    offsets = torch.searchsorted(by_list, torch.arange(nlist + 1, dtype=list_ids.dtype,
+                                                       device=list_ids.device))
+    return perm, offsets.to(torch.int64)
+
+
+def probe_ranges(offsets, probes):
+    """(range_ptr, ranges) for search_ranges from ivf_layout's offsets and the lists each query
+    probes: probes int64 (nq, nprobe), an entry of -1 probing nothing (an empty range, so
+    range_ptr is arange(nq + 1) * nprobe and nothing is compacted).  No sync."""
+    torch = _torch()
+    nq, nprobe = probes.shape
+    lists = probes.reshape(-1)
+    none = lists < 0
+    lists = lists.clamp(min=0)
+    first = offsets[lists]
+    count = offsets[lists + 1] - first
+    zero = torch.zeros_like(first)
+    ranges = torch.stack((torch.where(none, zero, first), torch.where(none, zero, count)), dim=1)
+    range_ptr = torch.arange(nq + 1, dtype=torch.int64, device=probes.device) * nprobe
+    return range_ptr, ranges.contiguous()
 
 
 def encode_status(ctx: Context) -> None:

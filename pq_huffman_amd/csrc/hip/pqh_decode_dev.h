@@ -311,10 +311,11 @@ __device__ __forceinline__ bool walk_parts(Rd& br, const DecTabs& T, int m, bool
 }
 
 // ------------------------------------------------------------------- the stream window
-// The 64 chunks [j0, j0 + 64) of a workgroup are contiguous in the stream, so their words
-// [w_lo, w_lo + nw) are copied into an LDS window with coalesced non-temporal loads (streamed
-// once, so the code tables keep the L2), FLIGHT loads in flight per lane, byte-swapped on the
-// way in for PosRd (SWAP), followed by a 4-word zero pad that reads past the data land in.
+// The `span` (64 unless the caller has fewer) chunks [j0, j0 + span) of a workgroup are
+// contiguous in the stream, so their words [w_lo, w_lo + nw) are copied into an LDS window
+// with coalesced non-temporal loads (streamed once, so the code tables keep the L2), FLIGHT
+// loads in flight per lane, byte-swapped on the way in for PosRd (SWAP), followed by a 4-word
+// zero pad that reads past the data land in.
 // A span longer than the window is left in global memory (in_lds = false).  No barrier here.
 struct StreamWin {
     long long w_lo, nw;
@@ -324,10 +325,10 @@ template <int FLIGHT, bool SWAP>
 __device__ __forceinline__ StreamWin stage_window(const uint32_t* __restrict__ words, long long nwords,
                                                   const unsigned long long* __restrict__ chunk_off,
                                                   long long j0, long long chunks, uint32_t* win,
-                                                  int win_words) {
+                                                  int win_words, int span = 64) {
     const int lane = threadIdx.x;
     const unsigned long long b_lo = chunk_off[j0];
-    const unsigned long long b_hi = j0 + 64 < chunks ? chunk_off[j0 + 64] : (unsigned long long)nwords * 32;
+    const unsigned long long b_hi = j0 + span < chunks ? chunk_off[j0 + span] : (unsigned long long)nwords * 32;
     const long long w_lo = (long long)(b_lo >> 5);
     const long long w_hi = min(nwords, (long long)((b_hi + 31) >> 5) + 2);
     const long long nw = w_hi - w_lo;

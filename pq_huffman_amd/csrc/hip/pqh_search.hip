@@ -10,6 +10,10 @@
 //              (one entry per lane, ascending by (dist, id)), merged per workgroup at the
 //              end.  The codes never reach memory.
 //              SRC = 1 loads plain u8 rows into the same stage instead of decoding them.
+//              RG = 1 (the probe search): every query has its own row ranges, so a workgroup
+//              holds one query's table (QB = 1) and its steps are those of adc_plan: a step
+//              is up to L chunks of one range, and only the rows inside the range are offered.
+//  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
 //  adc_merge   one workgroup per query: every scan workgroup's list through the same list code.
 //
 // dist(v) = ((lut[0][c_0] + lut[1][c_1]) + ...) + lut[m-1][c_{m-1}] in fp32, the order total
@@ -26,6 +30,8 @@ namespace {
 constexpr int kScanWavesMax = 16;          // waves per workgroup (threadIdx.y; threadIdx.x = lane)
 constexpr int kLdsBytes = 160 * 1024;
 constexpr int kCodesRowsPerLane = 4;       // SRC = 1: a wave stages 64 * 4 rows per step
+constexpr int kRangeWaves = 4;             // the probe search: waves per workgroup, and how many
+constexpr int kRangeFill = 4;              // times over its workgroups fill the compute units
 
 __global__ void __launch_bounds__(256)
 adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
@@ -169,11 +175,69 @@ struct ScanArgs {
     float* part_d;              // [nq][groups][top_k]: one list per workgroup and query
     long long* part_id;
     unsigned long long* err;
+    // RG: the probe list in CSR form (device data, checked on the device) and adc_plan's prefix
+    const long long* range_ptr; // [nq + 1]
+    const long long* ranges;    // [nr][2]: first row, count
+    long long nr;
+    const long long* plan;      // [nr + 1]
 };
 
-template <int SRC, int NW, bool CTX, int QB>
+// The chunks of a good range: [first / C, (first + count - 1) / C + 1); a range is good when
+// 0 <= first <= n and 0 <= count <= n - first (no sum that could overflow).
+__device__ __forceinline__ bool range_ok(long long first, long long count, long long n) {
+    return first >= 0 && count >= 0 && first <= n && count <= n - first;
+}
+
+// plan[r] = the steps of the ranges before r, plan[nr] = all of them: a range of count > 0
+// rows takes ceil(its chunks / L) steps, an empty or a bad one none (so no step ever leads to
+// it), and a bad one sets error bit 2.  The prefix is over all ranges, not per query: the
+// queries' spans of it may overlap or repeat, and query q's steps are
+// [plan[range_ptr[q]], plan[range_ptr[q + 1]]) whatever the others are.  One workgroup:
+// 1,024 ranges a round, the wave's sums by shuffles, the waves' through LDS.
+constexpr int kPlanWaves = 16;
+__global__ void __launch_bounds__(64 * kPlanWaves)
+adc_plan(const long long* __restrict__ ranges, long long nr, long long n, int C, int L,
+         long long* __restrict__ plan, unsigned long long* __restrict__ err) {
+    __shared__ long long wsum[kPlanWaves];
+    const int lane = threadIdx.x;
+    const int wave = threadIdx.y;
+    long long carry = 0;
+    bool bad = false;
+    for (long long base = 0; base < nr; base += 64 * kPlanWaves) {
+        const long long r = base + wave * 64 + lane;
+        long long s = 0;
+        if (r < nr) {
+            const long long first = ranges[2 * r], count = ranges[2 * r + 1];
+            if (!range_ok(first, count, n))
+                bad = true;
+            else if (count > 0)
+                s = ((first + count - 1) / C - first / C + L) / L;   // ceil(chunks / L)
+        }
+        long long inc = s;   // the wave's inclusive prefix
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long t = __shfl_up(inc, d);
+            inc += lane >= d ? t : 0;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        lds_barrier();
+        long long before = 0, all = 0;
+        for (int w = 0; w < kPlanWaves; ++w) {
+            before += w < wave ? wsum[w] : 0;
+            all += wsum[w];
+        }
+        if (r < nr) plan[r] = carry + before + inc - s;
+        carry += all;
+        lds_barrier();   // (wsum is written again in the next round)
+    }
+    if (wave == 0 && lane == 0) plan[nr] = carry;
+    if (bad) atomicOr(err, 2ull);
+}
+
+template <int SRC, int NW, bool CTX, int QB, bool RG = false>
 __global__ void __launch_bounds__(64 * kScanWavesMax)
 adc_scan(const ScanArgs a) {
+    static_assert(RG == (QB == 1), "one query per workgroup is the probe search's form");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int lane = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
@@ -198,8 +262,26 @@ adc_scan(const ScanArgs a) {
         for (int u = 0; u < QB / 4; ++u)
             reinterpret_cast<float4*>(lut_lds + (size_t)e * QB)[u] =
                 make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+        if constexpr (QB == 1) lut_lds[e] = v[0];
     }
     lds_barrier();
+
+    // RG: the query's ranges [r_lo, r_hi) and its steps [t0, t0 + steps) of the plan; range_ptr
+    // entries that are reversed or leave [0, nr] leave the query without steps (error bit 2)
+    long long steps = a.steps;
+    long long r_lo = 0, r_hi = 0, t0 = 0;
+    if constexpr (RG) {
+        const long long p0 = a.range_ptr[q0], p1 = a.range_ptr[q0 + 1];
+        steps = 0;
+        if (p0 >= 0 && p0 <= p1 && p1 <= a.nr) {
+            r_lo = p0;
+            r_hi = p1;
+            t0 = a.plan[p0];
+            steps = a.plan[p1] - t0;
+        } else if (blockIdx.y == 0 && wave == 0 && lane == 0) {
+            atomicOr(a.err, 2ull);
+        }
+    }
 
     TopK list[QB];
 #pragma unroll
@@ -209,26 +291,47 @@ adc_scan(const ScanArgs a) {
     const long long chunks = (a.n + C - 1) / C;
     const unsigned long long nbits = (unsigned long long)a.nwords * 32;
     // this workgroup's span of steps; its waves take them in turn
-    const long long g_lo = (long long)blockIdx.y * a.steps / gridDim.y;
-    const long long g_hi = ((long long)blockIdx.y + 1) * a.steps / gridDim.y;
+    const long long g_lo = (long long)blockIdx.y * steps / gridDim.y;
+    const long long g_hi = ((long long)blockIdx.y + 1) * steps / gridDim.y;
+    long long r_cur = r_lo;   // RG: the range of the wave's last step (its steps ascend)
 #pragma unroll 1
     for (long long g = g_lo + wave; g < g_hi; g += waves) {
-        const long long j0 = g * a.L;
-        const long long jn = min(chunks - j0, (long long)a.L);
+        long long j0 = g * a.L;
+        long long jn = min(chunks - j0, (long long)a.L);
+        long long lo = 0, hi = 0;   // RG: the step's rows inside its range are [lo, hi)
+        if constexpr (RG) {
+            // the step's range: the last one of [r_cur, r_hi) whose steps begin at or before
+            // it (ranges without steps share their successor's entry and are passed over)
+            const long long t = t0 + g;
+            long long e = r_hi;
+            while (e - r_cur > 1) {
+                const long long mid = r_cur + (e - r_cur) / 2;
+                if (a.plan[mid] <= t)
+                    r_cur = mid;
+                else
+                    e = mid;
+            }
+            const long long first = a.ranges[2 * r_cur], count = a.ranges[2 * r_cur + 1];
+            j0 = first / C + (t - a.plan[r_cur]) * a.L;
+            jn = min((first + count - 1) / C + 1 - j0, (long long)a.L);
+            lo = max(first, j0 * C);
+            hi = min(first + count, (j0 + jn) * C);
+        }
         const long long row0 = j0 * C;
-        const int nrows = (int)(min(a.n, (j0 + a.L) * C) - row0);
+        const int nrows = (int)(min(a.n, (j0 + (RG ? jn : (long long)a.L)) * C) - row0);
+        const int span = RG ? (int)jn : 64;   // the chunks the stream window is staged for
         unsigned long long dead = 0;   // lanes whose chunk failed
         if constexpr (SRC == 0) {
             bool use_win = false;
             StreamWin sw{0, 0, false};
             if (a.win_words > 0) {   // (then L = 64: the window is that of 64 chunks)
                 const unsigned long long b_lo = a.chunk_off[j0];
-                const unsigned long long b_hi = j0 + 64 < chunks ? a.chunk_off[j0 + 64] : nbits;
+                const unsigned long long b_hi = j0 + span < chunks ? a.chunk_off[j0 + span] : nbits;
                 // (an index that does not ascend or leaves the stream: no window, every
                 // lane's own offset is then checked by SelRd)
                 if (b_lo <= nbits && b_hi >= b_lo) {
                     sw = stage_window<4, true>(a.words, a.nwords, a.chunk_off, j0, chunks, win,
-                                               a.win_words);
+                                               a.win_words, span);
                     use_win = sw.in_lds;
                 }
             }
@@ -237,7 +340,8 @@ adc_scan(const ScanArgs a) {
             if (lane < jn) {
                 const long long j = j0 + lane;
                 const unsigned long long off = a.chunk_off[j];
-                const int cnt = (int)min((long long)C, a.n - j * C);
+                // (RG: a chunk cut by the range's end is decoded up to that end only)
+                const int cnt = (int)min((long long)C, (RG ? hi : a.n) - j * C);
                 const bool raw = CTX && j == 0 && a.raw_first;
                 auto walk = [&](auto& br) -> bool {
                     if constexpr (NW > 0) {
@@ -312,10 +416,18 @@ adc_scan(const ScanArgs a) {
             const int r = base + lane;
             bool valid = r < nrows;
             if (dead && valid) valid = !((dead >> (r / C)) & 1ull);
+            if constexpr (RG) valid = valid && row0 + r >= lo && row0 + r < hi;
             const unsigned char* row = stage + (long long)(r < nrows ? r : 0) * m;
             float sum[QB];
             auto add = [&](int i, unsigned c) {
                 // (a failed chunk's slots hold anything: keep the read inside the table)
+                if constexpr (QB == 1) {   // one ds_read_b32 a part
+                    const float v = lut_lds[i * k + (int)min(c, (unsigned)(k - 1))];
+                    if (i == 0)
+                        sum[0] = v;
+                    else
+                        sum[0] = sum[0] + v;
+                }
                 const float4* e = reinterpret_cast<const float4*>(
                     lut_lds + (size_t)(i * k + (int)min(c, (unsigned)(k - 1))) * QB);
 #pragma unroll
@@ -461,14 +573,15 @@ int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long lon
 }
 
 // the scan and the merge; a.C, a.n, a.m, a.k and the source are set by the caller, nw = the
-// row's u64 words (0: per part)
+// row's u64 words (0: per part).  rg: the probe search (a.range_ptr, a.ranges and a.nr set):
+// the plan first, then one query per workgroup.
 int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long id_base,
-                float* d_dist, long long* d_ids) {
+                float* d_dist, long long* d_ids, bool rg = false) {
     if (a.nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
     const int m = a.m, k = a.k;
     // the batch's tables: at most 64 KB; 16-part rows keep to four queries (eight running
     // sums beside sixteen unrolled parts spill registers)
-    const int qb = (m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
+    const int qb = rg ? 1 : (m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
     const long long lut_bytes = (long long)m * k * qb * 4;
     const long long budget = kLdsBytes - lut_bytes;
     const long long chunks = (a.n + a.C - 1) / a.C;
@@ -489,28 +602,50 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         if (a.stage_bytes + (a.win_words + 4) * 4 > budget) a.win_words = 0;
     }
     const long long per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
-    const int fit = floor_pow2(std::min<long long>(kScanWavesMax, budget / per_wave));
+    int fit = floor_pow2(std::min<long long>(kScanWavesMax, budget / per_wave));
     a.steps = (chunks + a.L - 1) / a.L;
     const long long batches = (a.nq + qb - 1) / qb;
     // one workgroup per compute unit over all query batches (a workgroup's tables take most
     // of a compute unit's LDS), each wave with at least two steps where there are that many
     long long groups = ctx->tune_search_groups > 0 ? ctx->tune_search_groups
                                                    : std::max<long long>(1, ctx->num_cus / batches);
-    groups = std::min<long long>(std::min<long long>(groups, a.steps), 65535);
-    const int waves = std::min(fit, floor_pow2((a.steps + 2 * groups - 1) / (2 * groups)));
+    if (rg) {
+        // A query's steps are known on the device only: the grid is fixed here.  One table
+        // leaves room for several workgroups of kRangeWaves waves on a compute unit, and
+        // nq * groups workgroups fill the compute units kRangeFill times over; a query has at
+        // most the stream's steps unless its ranges overlap.
+        fit = std::min(fit, kRangeWaves);
+        if (ctx->tune_search_groups <= 0)
+            groups = std::min<long long>(
+                (kRangeFill * (long long)ctx->num_cus + a.nq - 1) / a.nq,
+                (a.steps + fit - 1) / fit);
+        groups = std::min<long long>(std::max<long long>(groups, 1), 65535);
+    } else {
+        groups = std::min<long long>(std::min<long long>(groups, a.steps), 65535);
+    }
+    const int waves =
+        rg ? fit : std::min(fit, floor_pow2((a.steps + 2 * groups - 1) / (2 * groups)));
     const long long lists = groups;   // (a workgroup merges its waves' lists)
     const size_t entries = (size_t)a.nq * lists * a.top_k;
-    int rc = pqh_ensure_ws(ctx, entries * 12 + 16);
+    const size_t plan_bytes = rg ? ((size_t)a.nr + 1) * 8 : 0;   // beside the partial lists
+    int rc = pqh_ensure_ws(ctx, entries * 12 + 16 + plan_bytes);
     if (rc) return rc;
     a.part_id = static_cast<long long*>(ctx->ws);
     a.part_d = reinterpret_cast<float*>(a.part_id + entries);
     a.err = ctx->d_diag + 1;
+    if (rg) {
+        long long* plan = static_cast<long long*>(ctx->ws) + ((entries * 12 + 15) / 8);
+        hipLaunchKernelGGL(adc_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, a.ranges, a.nr,
+                           a.n, a.C, a.L, plan, a.err);
+        PQH_LAUNCH_CHECK(ctx);
+        a.plan = plan;
+    }
     // (the end of the kernel exchanges the waves' lists, 12 bytes an entry, through the same LDS)
     const size_t lds = std::max<size_t>((size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
                                         (size_t)waves * qb * 64 * 12);
     auto launch = [&](auto s, auto w, auto c, auto q) -> int {
         auto* fn = adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
-                            decltype(q)::value>;
+                            decltype(q)::value, decltype(q)::value == 1>;
         if (lds > 64 * 1024)
             PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -519,6 +654,7 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         return PQH_OK;
     };
     auto with_qb = [&](auto s, auto w, auto c) -> int {
+        if (rg) return launch(s, w, c, Int<1>());
         if constexpr (decltype(w)::value != 2)
             if (qb == 8) return launch(s, w, c, Int<8>());
         return launch(s, w, c, Int<4>());
@@ -551,6 +687,86 @@ int search_check(pqh_ctx_t* ctx, bool have_src, long long n, const float* d_lut,
     return PQH_OK;
 }
 
+// the probe list's host-side checks (its values are device data: adc_plan and adc_scan)
+bool ranges_args_ok(long long nq, const long long* d_range_ptr, const long long* d_ranges,
+                    long long nr) {
+    return nr >= 0 && !(nq > 0 && (!d_range_ptr || (nr > 0 && !d_ranges)));
+}
+
+// the probe list of the *_ranges calls
+struct Probe {
+    const long long* range_ptr;
+    const long long* ranges;
+    long long nr;
+};
+
+// pqh_search_stream (pr = null) and pqh_search_stream_ranges
+int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                  unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
+                  const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
+                  const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
+                  float* d_dist, long long* d_ids) {
+    if (!ctx) return no_ctx_status();
+    if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
+    if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
+    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
+    if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
+    if (t->k > 256 || t->m > 16) return PQH_ERR_UNSUPPORTED;
+    bool run = false;
+    int rc = search_check(ctx, d_stream != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
+    if (rc || !run) return rc;
+    if (pr && pr->nr == 0)
+        return merge_launch(ctx, nullptr, nullptr, 0, nq, top_k, id_base, d_dist, d_ids);
+    if (stream_bytes / 4 >= (1ull << 58)) return PQH_ERR_UNSUPPORTED;
+    ScanArgs a{};
+    a.words = reinterpret_cast<const uint32_t*>(d_stream);
+    a.nwords = (long long)(stream_bytes / 4);
+    a.chunk_off = d_chunk_offsets;
+    a.chunk_prev = d_chunk_prev;
+    a.T = dec_tabs(t, 0);
+    a.raw_first = raw_first;
+    a.n = n;
+    a.m = t->m;
+    a.k = t->k;
+    a.C = chunk_vectors;
+    a.lut = d_lut;
+    a.nq = nq;
+    a.top_k = top_k;
+    if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
+    // rows of whole u64 words with the chunk contexts readable as such: the packed walk
+    const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
+    return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, id_base, d_dist, d_ids,
+                       pr != nullptr);
+}
+
+// pqh_search_codes (pr = null) and pqh_search_codes_ranges
+int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                 const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
+                 float* d_dist, long long* d_ids) {
+    if (!ctx) return no_ctx_status();
+    if (m < 1 || k < 1) return PQH_ERR_ARG;
+    if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
+    if (k > 256 || m > 16) return PQH_ERR_UNSUPPORTED;
+    bool run = false;
+    int rc = search_check(ctx, d_codes != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
+    if (rc || !run) return rc;
+    if (pr && pr->nr == 0)
+        return merge_launch(ctx, nullptr, nullptr, 0, nq, top_k, id_base, d_dist, d_ids);
+    ScanArgs a{};
+    a.codes = static_cast<const unsigned char*>(d_codes);
+    a.n = n;
+    a.m = m;
+    a.k = k;
+    a.C = kCodesRowsPerLane;
+    a.lut = d_lut;
+    a.nq = nq;
+    a.top_k = top_k;
+    if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
+    return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids,
+                       pr != nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -580,54 +796,35 @@ int pqh_search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char
                       int chunk_vectors, const unsigned long long* d_chunk_offsets,
                       const void* d_chunk_prev, const float* d_lut, long long nq, int top_k,
                       long long id_base, float* d_dist, long long* d_ids) {
-    if (!ctx) return no_ctx_status();
-    if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
-    if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
-    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
-    if (t->k > 256 || t->m > 16) return PQH_ERR_UNSUPPORTED;
-    bool run = false;
-    int rc = search_check(ctx, d_stream != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
-    if (rc || !run) return rc;
-    if (stream_bytes / 4 >= (1ull << 58)) return PQH_ERR_UNSUPPORTED;
-    ScanArgs a{};
-    a.words = reinterpret_cast<const uint32_t*>(d_stream);
-    a.nwords = (long long)(stream_bytes / 4);
-    a.chunk_off = d_chunk_offsets;
-    a.chunk_prev = d_chunk_prev;
-    a.T = dec_tabs(t, 0);
-    a.raw_first = raw_first;
-    a.n = n;
-    a.m = t->m;
-    a.k = t->k;
-    a.C = chunk_vectors;
-    a.lut = d_lut;
-    a.nq = nq;
-    a.top_k = top_k;
-    // rows of whole u64 words with the chunk contexts readable as such: the packed walk
-    const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
-    return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, id_base, d_dist, d_ids);
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, nullptr, top_k, id_base, d_dist,
+                         d_ids);
 }
 
 int pqh_search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                      const float* d_lut, long long nq, int top_k, long long id_base,
                      float* d_dist, long long* d_ids) {
-    if (!ctx) return no_ctx_status();
-    if (m < 1 || k < 1) return PQH_ERR_ARG;
-    if (k > 256 || m > 16) return PQH_ERR_UNSUPPORTED;
-    bool run = false;
-    int rc = search_check(ctx, d_codes != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
-    if (rc || !run) return rc;
-    ScanArgs a{};
-    a.codes = static_cast<const unsigned char*>(d_codes);
-    a.n = n;
-    a.m = m;
-    a.k = k;
-    a.C = kCodesRowsPerLane;
-    a.lut = d_lut;
-    a.nq = nq;
-    a.top_k = top_k;
-    return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids);
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, nullptr, top_k, id_base, d_dist, d_ids);
+}
+
+int pqh_search_stream_ranges(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                             unsigned long long stream_bytes, long long n, int raw_first,
+                             int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                             const void* d_chunk_prev, const float* d_lut, long long nq,
+                             const long long* d_range_ptr, const long long* d_ranges, long long nr,
+                             int top_k, long long id_base, float* d_dist, long long* d_ids) {
+    const Probe pr{d_range_ptr, d_ranges, nr};
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, &pr, top_k, id_base, d_dist,
+                         d_ids);
+}
+
+int pqh_search_codes_ranges(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                            const float* d_lut, long long nq, const long long* d_range_ptr,
+                            const long long* d_ranges, long long nr, int top_k, long long id_base,
+                            float* d_dist, long long* d_ids) {
+    const Probe pr{d_range_ptr, d_ranges, nr};
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, &pr, top_k, id_base, d_dist, d_ids);
 }
 
 }  // extern "C"
