@@ -416,6 +416,70 @@ int pqh_search_codes_ranges(pqh_ctx_t* ctx, const void* d_codes, long long n, in
                             const long long* d_ranges, long long nr, int top_k, long long id_base,
                             float* d_dist, long long* d_ids);
 
+/* ---- inverted file: coarse quantizer, list layout, probe selection ---------------------
+ * The front end of the probe search: rows are assigned to the nearest of nlist coarse
+ * centroids (full d-dimensional vectors), stored list by list, and a query probes the nprobe
+ * lists nearest to it.  pqh_coarse_probe writes the CSR probe list pqh_search_*_ranges take,
+ * on the device, so the whole path from queries to neighbour ids runs without a host round
+ * trip.
+ * Conventions of the search calls: device pointers unless said otherwise, asynchronous on the
+ * context's stream; a NULL context returns PQH_ERR_NO_DEVICE when no HIP device is visible and
+ * PQH_ERR_ARG otherwise, checked before anything else.
+ * The distance is dist(x, c) = sum_j (x[j] - c[j])^2 in fp32, the direct form: one subtract,
+ * one multiply and one add per element, j ascending, no contraction -- the arithmetic of
+ * pqh_pq_assign and pqh_adc_tables.  The order is (dist, list id) ascending, so the first of
+ * several equal minima wins and every result is unique and independent of the launch shape.
+ * Results for NaN or infinite inputs (or sums that overflow) are unspecified; nothing is read
+ * or written out of bounds in any case.
+ * Limits: 1 <= d <= PQH_IVF_MAX_D and 1 <= nlist <= PQH_IVF_MAX_NLIST, any d (no multiple of
+ * anything); beyond them PQH_ERR_UNSUPPORTED.  pqh_ivf_layout takes n < 2^31 rows,
+ * pqh_coarse_probe nq < 2^31 queries. */
+typedef struct pqh_coarse pqh_coarse_t;
+#define PQH_IVF_MAX_NPROBE 64          /* = PQH_SEARCH_MAX_K: the same wave-wide list */
+#define PQH_IVF_MAX_NLIST (1 << 24)
+#define PQH_IVF_MAX_D 65536
+
+/* centroids: HOST [nlist][d] fp32.  The device keeps two copies, [nlist][d] for the assignment
+ * and [d][nlist] for the probe selection (8 * nlist * d bytes); synchronous. */
+int pqh_coarse_create(pqh_ctx_t* ctx, const float* centroids, int nlist, int d, pqh_coarse_t** cq);
+/* Synchronises the stream of the context it was made with, which must still exist. */
+int pqh_coarse_destroy(pqh_coarse_t* cq);
+
+/* d_list[v] = argmin_l dist(x[v], c[l]), the first minimum.  d_list int32 [n]; rows ld_x >= d
+ * floats apart, the floats between rows never read.  d_dist (optional, may be NULL): float
+ * [n], the winning distance.  n == 0 launches nothing. */
+int pqh_coarse_assign(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
+                      long long ld_x, int32_t* d_list, float* d_dist);
+
+/* Stable order of the rows by list: d_perm int64 [n] (stream row s holds caller row perm[s]),
+ * d_offsets int64 [nlist + 1] (list l = stream rows [offsets[l], offsets[l+1])).  A list id
+ * outside [0, nlist) writes nothing out of bounds and makes pqh_ivf_status answer PQH_ERR_ARG
+ * (d_perm is then still a permutation of the rows, otherwise unspecified, as d_offsets).
+ * n == 0: offsets all zero.
+ * Scratch: 4 * n bytes and rocPRIM's sort storage (about 12 * n) in the context workspace,
+ * freed by pqh_ctx_release_scratch. */
+int pqh_ivf_layout(pqh_ctx_t* ctx, const int32_t* d_list, long long n, int nlist,
+                   long long* d_perm, long long* d_offsets);
+
+/* For each query the nprobe nearest lists by (dist, l) ascending, written as the CSR probe
+ * list pqh_search_*_ranges take: d_range_ptr[q] = q * nprobe (int64 [nq + 1]);
+ * d_ranges[q * nprobe + p] = (offsets[l], offsets[l+1] - offsets[l]) (int64 [nq * nprobe][2]).
+ * Optional (may be NULL): d_probes int64 [nq][nprobe] and d_probe_dist float [nq][nprobe].
+ * nprobe > nlist: the tail is list -1, +inf, range (0, 0).  1 <= nprobe <= PQH_IVF_MAX_NPROBE,
+ * else PQH_ERR_ARG.  d_offsets (int64 [nlist + 1]) is device data and is not validated beyond
+ * what safety needs: an entry pair that is reversed gives the range (0, 0) and PQH_ERR_ARG
+ * from pqh_ivf_status; whether the ranges fit the stream is checked by the search that takes
+ * them.  Query rows are ld_q >= d floats apart.  nq == 0 launches nothing.
+ * One workgroup per query: the time grows with nlist * d per query. */
+int pqh_coarse_probe(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_queries, long long nq,
+                     long long ld_q, int nprobe, const long long* d_offsets,
+                     long long* d_range_ptr, long long* d_ranges, long long* d_probes,
+                     float* d_probe_dist);
+
+/* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe on this context since the
+ * last call met a bad value (sticky until read, like pqh_decode_status). */
+int pqh_ivf_status(pqh_ctx_t* ctx);
+
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by
  * the reference encoder) with a sequential table walk on the HOST copy of the stream
  * (index building only; the symbols themselves are decoded on the GPU). */

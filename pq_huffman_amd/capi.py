@@ -158,6 +158,11 @@ SIGNATURES = [
     ("pqh_search_codes", I, [P, P, LL, I, I, P, LL, I, LL, P, P]),
     ("pqh_search_stream_ranges", I, [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, LL, P, P]),
     ("pqh_search_codes_ranges", I, [P, P, LL, I, I, P, LL, P, P, LL, I, LL, P, P]),
+    ("pqh_coarse_create", I, [P, P, I, I, P]), ("pqh_coarse_destroy", I, [P]),
+    ("pqh_coarse_assign", I, [P, P, P, LL, LL, P, P]),
+    ("pqh_ivf_layout", I, [P, P, LL, I, P, P]),
+    ("pqh_coarse_probe", I, [P, P, P, LL, LL, I, P, P, P, P, P]),
+    ("pqh_ivf_status", I, [P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

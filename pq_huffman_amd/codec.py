@@ -13,11 +13,14 @@ calls on device-resident data:
     decode               huffman_decoder.c:206-255
     search               ADC top-k over the stream, fused into the decoder (no reference analogue)
     search_ranges        the same over per-query row ranges: the probe search of an inverted file
+    Coarse, IVF          the front end of that search: rows to lists, the list layout, each
+                         query's probe list, and the whole path from vectors to neighbour ids
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
-(a sort and gathers of int64 in plain torch).  Device buffers are torch tensors owned by the
-caller.
+(a sort and gathers of int64 in plain torch; Coarse.layout and Coarse.probe are their libpqh
+forms) and IVF's gathers through its permutation.  Device buffers are torch tensors owned by
+the caller.
 """
 from __future__ import annotations
 
@@ -703,6 +706,137 @@ def probe_ranges(offsets, probes):
     ranges = torch.stack((torch.where(none, zero, first), torch.where(none, zero, count)), dim=1)
     range_ptr = torch.arange(nq + 1, dtype=torch.int64, device=probes.device) * nprobe
     return range_ptr, ranges.contiguous()
+
+
+class Coarse:
+    """The coarse quantizer of an inverted file (pqh_coarse_t): nlist centroids of full
+    d-dimensional vectors on the device.  centroids: host float32 (nlist, d) -- or
+    (1, nlist, d), as kmeans_train(m = 1, k = nlist, dsub = d) returns them.  Distances are the
+    direct form in fp32 (the arithmetic of PQ.assign and adc_tables), ties go to the smaller
+    list id."""
+
+    def __init__(self, ctx: Context, centroids: np.ndarray):
+        c = np.ascontiguousarray(centroids, np.float32)
+        if c.ndim == 3 and c.shape[0] == 1:
+            c = c[0]
+        self.nlist, self.d = c.shape
+        self.ctx = ctx
+        self.ptr = ctypes.c_void_p()
+        check(lib().pqh_coarse_create(ctx.ptr, _ptr(c), self.nlist, self.d,
+                                      ctypes.byref(self.ptr)), "pqh_coarse_create")
+        ctx._retain()
+
+    def assign(self, x, out=None, dist=None):
+        """list ids int32 (n,) of the rows of x (device float32 (n, >= d)), the nearest
+        centroid each (pqh_coarse_assign); dist: an optional float32 (n,) tensor that takes the
+        winning distances.  Async."""
+        torch = _torch()
+        n = x.shape[0]
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=x.device)
+        check(lib().pqh_coarse_assign(self.ctx.ptr, self.ptr, _ptr(x), n, x.stride(0), _ptr(out),
+                                      _ptr(dist)), "pqh_coarse_assign")
+        return out
+
+    def layout(self, list_ids):
+        """(perm, offsets) as ivf_layout gives them, by pqh_ivf_layout: list_ids device int32
+        (n,).  Async; ivf_status reports an id outside [0, nlist)."""
+        torch = _torch()
+        if list_ids.dtype != torch.int32 or not list_ids.is_contiguous():
+            list_ids = list_ids.to(torch.int32).contiguous()
+        n = list_ids.numel()
+        perm = torch.empty(n, dtype=torch.int64, device=list_ids.device)
+        offsets = torch.empty(self.nlist + 1, dtype=torch.int64, device=list_ids.device)
+        check(lib().pqh_ivf_layout(self.ctx.ptr, _ptr(list_ids), n, self.nlist, _ptr(perm),
+                                   _ptr(offsets)), "pqh_ivf_layout")
+        return perm, offsets
+
+    def probe(self, queries, nprobe: int, offsets, lists: bool = True):
+        """(range_ptr, ranges, probes, probe_dist): for every query (device float32
+        (nq, >= d)) its nprobe nearest lists by (dist, list id) and their row ranges in the CSR
+        form search_ranges takes (pqh_coarse_probe).  probes int64 (nq, nprobe) and probe_dist
+        float32 (nq, nprobe), padded with (-1, +inf) and the range (0, 0) when nprobe > nlist;
+        lists=False leaves the two out (None).  Async, no sync."""
+        torch = _torch()
+        nq = queries.shape[0]
+        dev = queries.device
+        range_ptr = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        ranges = torch.empty((nq * nprobe, 2), dtype=torch.int64, device=dev)
+        probes = torch.empty((nq, nprobe), dtype=torch.int64, device=dev) if lists else None
+        pdist = torch.empty((nq, nprobe), dtype=torch.float32, device=dev) if lists else None
+        check(lib().pqh_coarse_probe(self.ctx.ptr, self.ptr, _ptr(queries), nq, queries.stride(0),
+                                     nprobe, _ptr(offsets), _ptr(range_ptr), _ptr(ranges),
+                                     _ptr(probes), _ptr(pdist)), "pqh_coarse_probe")
+        return range_ptr, ranges, probes, pdist
+
+    def close(self):
+        if self.ptr:
+            lib().pqh_coarse_destroy(self.ptr)
+            self.ptr = ctypes.c_void_p()
+            self.ctx._release()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ivf_status(ctx: Context) -> None:
+    """raises PQH_ERR_ARG if a Coarse.layout / Coarse.probe since the last call met a bad value
+    (a list id outside [0, nlist), a reversed offsets pair); synchronises (pqh_ivf_status)"""
+    st = lib().pqh_ivf_status(ctx.ptr)
+    if st:
+        raise PqhError(st, "pqh_ivf")
+
+
+class IVF:
+    """An inverted-file index over a compressed stream: the rows of x assigned to the lists
+    of a coarse quantizer, stored list by list as one Huffman-coded PQ stream, and searched by
+    probing each query's nearest lists.  ids are rows of the caller's x.
+
+    The order of a result is (dist, stream row), that is (dist, list, caller row): rows of
+    equal distance come list by list, NOT in caller-row order.
+
+    Every stage is a call on the context's stream.  search() never waits for the device;
+    build() waits where encode() does, once, for the stream's length."""
+
+    def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets):
+        self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
+        self.perm, self.inv, self.offsets = perm, inv, offsets
+
+    @classmethod
+    def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
+              context: bool = True) -> "IVF":
+        """x: device float32 (n, d), d = coarse.d = pq.m * pq.dsub.  The stages: rows to
+        lists, layout, gather x[perm], pq.assign, histogram, Tables.build, encode."""
+        torch = _torch()
+        if pq.k > 256 or pq.m > 16:
+            raise PqhError(-4, "IVF.build: the search takes K <= 256 and m <= 16")
+        if coarse.d != pq.m * pq.dsub or x.shape[1] != coarse.d:
+            raise PqhError(-1, "IVF.build: x, the coarse centroids and the PQ disagree in d")
+        perm, offsets = coarse.layout(coarse.assign(x))
+        codes = pq.assign(x[perm], ctx=ctx)
+        counts = histogram(ctx, codes, pq.k, context)
+        tables = Tables(ctx, pq.m, pq.k, context).build(counts)
+        enc = encode(ctx, tables, codes, chunk_vectors=chunk_vectors)
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
+        return cls(ctx, pq, coarse, tables, enc, perm, inv, offsets)
+
+    def search(self, queries, nprobe: int, k: int):
+        """(dist, ids), each (nq, k): the k nearest rows by ADC distance among the rows of each
+        query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1)."""
+        torch = _torch()
+        lut = adc_tables(self.ctx, self.pq, queries)
+        range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False)
+        dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k)
+        return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
+
+    def fetch(self, ids, out=None):
+        """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)), for
+        an exact re-rank (fetch through the inverse permutation)"""
+        return fetch(self.ctx, self.tables, self.pq, self.enc, self.inv[ids.reshape(-1)], out)
 
 
 def encode_status(ctx: Context) -> None:

@@ -37,6 +37,15 @@ bool pqh_debug_sync() {
     return v == 1;
 }
 
+int pqh_no_ctx_status() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        return PQH_ERR_NO_DEVICE;
+    }
+    return PQH_ERR_ARG;
+}
+
 int pqh_use_device(pqh_ctx* ctx) {
     PQH_HIP(ctx, hipSetDevice(ctx->device));
     return PQH_OK;
@@ -109,8 +118,8 @@ int pqh_ctx_create(pqh_ctx_t** out, int device) {
         return PQH_ERR_HIP;
     }
     ctx->own_stream = true;
-    if (hipMalloc(&ctx->d_diag, 8 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(ctx->d_diag, 0, 8 * sizeof(unsigned long long)) != hipSuccess ||
+    if (hipMalloc(&ctx->d_diag, kDiagSlots * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(ctx->d_diag, 0, kDiagSlots * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&ctx->d_sched, (size_t)2 * kSchedSet * sizeof(uint32_t)) != hipSuccess ||
         hipMemset(ctx->d_sched, 0, (size_t)2 * kSchedSet * sizeof(uint32_t)) != hipSuccess) {
         if (ctx->d_diag) (void)hipFree(ctx->d_diag);

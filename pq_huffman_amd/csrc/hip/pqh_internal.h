@@ -30,7 +30,8 @@ struct pqh_ctx {
     size_t ws_bytes = 0;
     // [0] / [4] re-rank counters of alternate assignment launches, [1] decode error,
     // [2] encode capacity error, [3] scratch total bits, [6] re-rank count of the exact path,
-    // [7] tree-order id error
+    // [5] sink of pqh_debug_poison_lds, [7] tree-order id error, [8] bad value met by
+    // pqh_ivf_layout / pqh_coarse_probe (sticky until pqh_ivf_status); kDiagSlots words
     unsigned long long* d_diag = nullptr;
     // one-pass encoder look-back state: [lb_cap] block states, [lb_cap] tails, ticket
     unsigned long long* lb_state = nullptr;
@@ -58,7 +59,9 @@ struct pqh_ctx {
     void* enc_scr = nullptr;
     size_t enc_scr_bytes = 0;
 };
-constexpr int kSchedMax = 64;      // subspaces with a work queue (more: static schedule)
+constexpr int kDiagSlots = 16;
+constexpr int kDiagIvf = 8;
+constexpr int kSchedMax = 64;     // subspaces with a work queue (more: static schedule)
 constexpr int kXcds = 8;
 constexpr int kSchedStride = 64;   // u32 words = 256 B
 constexpr long long kSchedSet = (long long)kSchedMax * kXcds * kSchedStride;   // words per set
@@ -67,6 +70,9 @@ int pqh_set_error(pqh_ctx* ctx, int code, const char* fmt, ...);
 int pqh_ensure_ws(pqh_ctx* ctx, size_t bytes);
 int pqh_ensure_enc_scratch(pqh_ctx* ctx, size_t bytes);
 int pqh_use_device(pqh_ctx* ctx);
+// what a call answers to a NULL context -- all a process without a GPU can have, since
+// pqh_ctx_create fails there: PQH_ERR_NO_DEVICE when no HIP device is visible, else PQH_ERR_ARG
+int pqh_no_ctx_status();
 int pqh_kmeans_fixed_shift(float max_abs, long long n);
 // k-means iteration pieces (pqh_kmeans.hip), shared by the one-shot and the streamed trainers
 int pqh_kmeans_absmax_launch(pqh_ctx* ctx, const float* d_x, long long n, long long ld_x, int d,

@@ -14,7 +14,8 @@
 //              holds one query's table (QB = 1) and its steps are those of adc_plan: a step
 //              is up to L chunks of one range, and only the rows inside the range are offered.
 //  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
-//  adc_merge   one workgroup per query: every scan workgroup's list through the same list code.
+//  adc_merge   one workgroup per query: every scan workgroup's list through the same list code
+//              (pqh_topk_dev.h, shared with the probe selection of pqh_ivf.hip).
 //
 // dist(v) = ((lut[0][c_0] + lut[1][c_1]) + ...) + lut[m-1][c_{m-1}] in fp32, the order total
 // (dist, then row id), so the result does not depend on the grid.
@@ -24,6 +25,7 @@
 
 #include "pqh_internal.h"
 #include "pqh_decode_dev.h"
+#include "pqh_topk_dev.h"
 
 namespace {
 
@@ -49,101 +51,6 @@ adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
         acc = acc + t * t;
     }
     lut[idx] = acc;
-}
-
-// ------------------------------------------------------------------- the top-k list
-// A wave's list: 64 entries, one per lane, ascending by (d, id); unused entries are
-// (+inf, -1), which every finite candidate precedes.  Only the first top_k lanes are the
-// result; the threshold a candidate has to beat is the entry of lane top_k - 1.
-struct TopK {
-    float d;
-    long long id;
-};
-
-__device__ __forceinline__ bool lex_lt(float a, long long ia, float b, long long ib) {
-    return (a < b) | ((a == b) & (ia < ib));   // (no short circuit: selects, not branches)
-}
-__device__ __forceinline__ float lane_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ long long lane_ll(long long v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), l);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ int wave_shr1(int v) {   // lane i takes lane i - 1 (lane 0 keeps v)
-    return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xF, 0xF, false);
-}
-
-// the wave-uniform candidate (cd, cid) into its place: its position is the number of entries
-// before it; the entries from there on move one lane up (the last one falls off)
-__device__ __forceinline__ void list_insert(TopK& e, float cd, long long cid) {
-    const int lane = threadIdx.x;
-    const int pos = __popcll(__ballot(lex_lt(e.d, e.id, cd, cid)));
-    const float pd = __int_as_float(wave_shr1(__float_as_int(e.d)));
-    const uint32_t plo = (uint32_t)wave_shr1((int)(uint32_t)e.id);
-    const uint32_t phi = (uint32_t)wave_shr1((int)(uint32_t)((unsigned long long)e.id >> 32));
-    const long long pid = (long long)(((unsigned long long)phi << 32) | plo);
-    e.d = lane > pos ? pd : lane == pos ? cd : e.d;
-    e.id = lane > pos ? pid : lane == pos ? cid : e.id;
-}
-
-// ---- many candidates at once: a bitonic network over the wave, one key per lane
-// the lane keeps the smaller (take_min) or the larger of its key and lane ^ j's
-__device__ __forceinline__ void key_exchange(TopK& x, int j, bool take_min) {
-    const TopK p{__shfl_xor(x.d, j), __shfl_xor(x.id, j)};
-    const bool take = take_min == lex_lt(p.d, p.id, x.d, x.id);
-    x.d = take ? p.d : x.d;
-    x.id = take ? p.id : x.id;
-}
-
-// The 64 smallest of the list and the 64 keys c, sorted, into the list.  c is sorted ascending
-// first unless it already is (SORTED); reversed, its lane-wise minimum with the list holds the
-// 64 smallest of both as a bitonic sequence, which six exchange steps sort.  Lanes without a
-// candidate carry (+inf, max id), which no list entry follows.
-template <bool SORTED>
-__device__ __forceinline__ void list_merge(TopK& e, TopK c) {
-    const int lane = threadIdx.x;
-    if constexpr (!SORTED) {
-#pragma unroll
-        for (int k = 2; k <= 64; k <<= 1)
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1)
-                key_exchange(c, j, ((lane & j) == 0) == ((lane & k) == 0));
-    }
-    const TopK r{__shfl(c.d, 63 - lane), __shfl(c.id, 63 - lane)};
-    const bool take = lex_lt(r.d, r.id, e.d, e.id);
-    e.d = take ? r.d : e.d;
-    e.id = take ? r.id : e.id;
-#pragma unroll
-    for (int j = 32; j > 0; j >>= 1) key_exchange(e, j, (lane & j) == 0);
-}
-
-// Every lane offers one candidate (d, id) (valid: it takes part).  The ones before the
-// threshold are inserted one by one, lowest lane first, the threshold moving with every insert
-// so that the rest are filtered again; more than kSerialMax of them go through list_merge
-// instead (an insert is a chain of ~50 dependent instructions, the network ~28 exchange steps
-// whatever the count).  SORTED: the candidates ascend with the lane.  Called by the whole wave.
-constexpr int kSerialMax = 6;
-template <bool SORTED>
-__device__ __forceinline__ void list_offer(TopK& e, float d, long long id, bool valid, int kth) {
-    float td = lane_f(e.d, kth);
-    long long tid = lane_ll(e.id, kth);
-    const bool pass = valid && lex_lt(d, id, td, tid);
-    unsigned long long mask = __ballot(pass);
-    if (!mask) return;
-    if (__popcll(mask) > kSerialMax) {
-        list_merge<SORTED>(e, pass ? TopK{d, id} : TopK{INFINITY, 0x7FFFFFFFFFFFFFFFll});
-        return;
-    }
-    while (mask) {
-        const int l = __builtin_ctzll(mask);
-        list_insert(e, lane_f(d, l), lane_ll(id, l));
-        td = lane_f(e.d, kth);
-        tid = lane_ll(e.id, kth);
-        mask &= mask - 1;
-        mask &= __ballot(valid && lex_lt(d, id, td, tid));
-    }
 }
 
 // LDS written by some lanes of this wave and read by others: all of it done before any lane
@@ -554,16 +461,6 @@ int floor_pow2(long long v) {
     return p;
 }
 
-// a NULL context is all a process without a GPU can have (pqh_ctx_create fails there)
-int no_ctx_status() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        return PQH_ERR_NO_DEVICE;
-    }
-    return PQH_ERR_ARG;
-}
-
 int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long long lists,
                  long long nq, int top_k, long long id_base, float* d_dist, long long* d_ids) {
     hipLaunchKernelGGL(adc_merge, dim3((unsigned)nq), dim3(64, kMergeWaves), 0, ctx->stream, pd,
@@ -706,7 +603,7 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
                   const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
                   const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
                   float* d_dist, long long* d_ids) {
-    if (!ctx) return no_ctx_status();
+    if (!ctx) return pqh_no_ctx_status();
     if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
     if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
@@ -744,7 +641,7 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
 int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                  const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
                  float* d_dist, long long* d_ids) {
-    if (!ctx) return no_ctx_status();
+    if (!ctx) return pqh_no_ctx_status();
     if (m < 1 || k < 1) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
     if (k > 256 || m > 16) return PQH_ERR_UNSUPPORTED;
@@ -773,7 +670,7 @@ extern "C" {
 
 int pqh_adc_tables(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
                    long long ld_q, float* d_lut) {
-    if (!ctx) return no_ctx_status();
+    if (!ctx) return pqh_no_ctx_status();
     int m = 0, k = 0, dsub = 0;
     const float* d_cent = nullptr;
     if (pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || nq < 0 || ld_q < (long long)m * dsub ||
