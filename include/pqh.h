@@ -416,6 +416,31 @@ int pqh_search_codes_ranges(pqh_ctx_t* ctx, const void* d_codes, long long n, in
                             const long long* d_ranges, long long nr, int top_k, long long id_base,
                             float* d_dist, long long* d_ids);
 
+/* The probe search with one table per range instead of one per query: d_lut is float
+ * [nr][m][K] and range r is scored with table r -- what a residual inverted file needs, where
+ * the table of a (query, list) pair is that of query - centroid[list]
+ * (pqh_adc_tables_residual).  Everything else is pqh_search_stream_ranges': the arguments,
+ * arithmetic, order (dist, stream row), padding, id_base, cut chunks, overlapping ranges, the
+ * bad values that are skipped and reported by pqh_decode_status, the chunks that are never
+ * read, the independence of the grid and the scratch.  With d_lut[r] = the table of the query
+ * that owns range r the result is pqh_search_stream_ranges' bit for bit.  The table of a range
+ * without rows (empty or bad) is never read. */
+int pqh_search_stream_range_tables(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                   const unsigned char* d_stream, unsigned long long stream_bytes,
+                                   long long n, int raw_first, int chunk_vectors,
+                                   const unsigned long long* d_chunk_offsets,
+                                   const void* d_chunk_prev, const float* d_lut /* [nr][m][K] */,
+                                   long long nq, const long long* d_range_ptr /* [nq + 1] */,
+                                   const long long* d_ranges /* [nr][2] */, long long nr,
+                                   int top_k, long long id_base, float* d_dist, long long* d_ids);
+
+/* The same over plain row-major u8 codes [n][m]. */
+int pqh_search_codes_range_tables(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                                  const float* d_lut /* [nr][m][K] */, long long nq,
+                                  const long long* d_range_ptr, const long long* d_ranges,
+                                  long long nr, int top_k, long long id_base, float* d_dist,
+                                  long long* d_ids);
+
 /* ---- inverted file: coarse quantizer, list layout, probe selection ---------------------
  * The front end of the probe search: rows are assigned to the nearest of nlist coarse
  * centroids (full d-dimensional vectors), stored list by list, and a query probes the nprobe
@@ -476,8 +501,40 @@ int pqh_coarse_probe(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_quer
                      long long* d_range_ptr, long long* d_ranges, long long* d_probes,
                      float* d_probe_dist);
 
-/* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe on this context since the
- * last call met a bad value (sticky until read, like pqh_decode_status). */
+/* The residual form of an inverted file: the stream holds the PQ codes of x - c[list], and a
+ * (query, probed list) pair is scored with the table of query - c[list].  The PQ codebook must
+ * then be trained on residuals (the output of pqh_ivf_residuals), not on x.
+ *
+ * d_out[s][j] = x[p][j] - c[d_list[p]][j] with p = d_perm ? d_perm[s] : s: the rows in list
+ * order and their residuals in one pass (one fp32 subtract per element).  d_list int32 [n] is
+ * indexed by caller row (pqh_coarse_assign's output), d_perm int64 [n] is pqh_ivf_layout's, or
+ * NULL for the identity.  Rows of x are ld_x >= d floats apart and rows of d_out ld_out >= d;
+ * the floats between rows of x are never read, those between rows of d_out never written.
+ * d_out must not overlap x.  A d_perm entry outside [0, n) or a list id outside [0, nlist)
+ * gives a row of zeros and PQH_ERR_ARG from pqh_ivf_status.  n == 0 launches nothing. */
+int pqh_ivf_residuals(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
+                      long long ld_x, const int32_t* d_list /* [n], by caller row */,
+                      const long long* d_perm /* [n] or NULL */, float* d_out, long long ld_out);
+
+/* One ADC table per (query, probed list): with l = d_probes[q][p] and r = query[q] - c[l] (one
+ * fp32 subtract per element), d_lut[q * nprobe + p][i][c] = sum_j (r[i*dsub+j] - cent[i][c][j])^2
+ * in pqh_adc_tables' arithmetic -- bit-equal to pqh_adc_tables run on r.  d_probes int64
+ * [nq][nprobe] is pqh_coarse_probe's; d_lut float [nq * nprobe][m][K] is what
+ * pqh_search_*_range_tables take beside pqh_coarse_probe's ranges.  l == -1 (the padding of
+ * pqh_coarse_probe) gives a table of +inf; any other l outside [0, nlist) the same and
+ * PQH_ERR_ARG from pqh_ivf_status.  PQH_ERR_ARG at once: pq's m * dsub != cq's d, nprobe < 1,
+ * ld_q < d, a null pointer when nq > 0.  PQH_ERR_UNSUPPORTED: K > 256,
+ * d > PQH_ADC_RESIDUAL_MAX_D (the residual is staged in LDS), nq * nprobe >= 2^31.
+ * nq == 0 launches nothing. */
+#define PQH_ADC_RESIDUAL_MAX_D 16384
+int pqh_adc_tables_residual(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse_t* cq,
+                            const float* d_queries, long long nq, long long ld_q,
+                            const long long* d_probes /* [nq][nprobe] */, int nprobe,
+                            float* d_lut /* [nq * nprobe][m][K] */);
+
+/* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe / pqh_ivf_residuals /
+ * pqh_adc_tables_residual on this context since the last call met a bad value (sticky until
+ * read, like pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
 
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by

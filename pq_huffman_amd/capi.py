@@ -163,6 +163,11 @@ SIGNATURES = [
     ("pqh_ivf_layout", I, [P, P, LL, I, P, P]),
     ("pqh_coarse_probe", I, [P, P, P, LL, LL, I, P, P, P, P, P]),
     ("pqh_ivf_status", I, [P]),
+    ("pqh_ivf_residuals", I, [P, P, P, LL, LL, P, P, P, LL]),
+    ("pqh_adc_tables_residual", I, [P, P, P, P, LL, LL, P, I, P]),
+    ("pqh_search_stream_range_tables", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, LL, P, P]),
+    ("pqh_search_codes_range_tables", I, [P, P, LL, I, I, P, LL, P, P, LL, I, LL, P, P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

@@ -15,11 +15,15 @@ calls on device-resident data:
     search_ranges        the same over per-query row ranges: the probe search of an inverted file
     Coarse, IVF          the front end of that search: rows to lists, the list layout, each
                          query's probe list, and the whole path from vectors to neighbour ids
+    search_range_tables  the probe search with one table per (query, list): the residual form
+                         of the inverted file (Coarse.residuals, adc_tables_residual,
+                         IVF.build(residual=True))
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
 (a sort and gathers of int64 in plain torch; Coarse.layout and Coarse.probe are their libpqh
-forms) and IVF's gathers through its permutation.  Device buffers are torch tensors owned by
+forms), IVF's gathers through its permutation and the centroid a residual IVF's fetch adds
+back (one torch add, not a hot path).  Device buffers are torch tensors owned by
 the caller.
 """
 from __future__ import annotations
@@ -679,6 +683,60 @@ def search_codes_ranges(ctx: Context, codes, lut, range_ptr, ranges, k: int, id_
     return dist, ids
 
 
+def adc_tables_residual(ctx: Context, pq: PQ, coarse: "Coarse", queries, probes, out=None):
+    """one ADC table per (query, probed list): float32 (nq * nprobe, m, K), table q * nprobe + p
+    that of queries[q] - centroid[probes[q, p]] in adc_tables' arithmetic
+    (pqh_adc_tables_residual).  probes: device int64 (nq, nprobe) as Coarse.probe returns them;
+    an entry of -1 gives a table of +inf.  Async; ivf_status reports any other entry outside
+    [0, nlist)."""
+    torch = _torch()
+    nq, nprobe = probes.shape
+    if not probes.is_contiguous():
+        probes = probes.contiguous()
+    if out is None:
+        out = torch.empty((nq * nprobe, pq.m, pq.k), dtype=torch.float32, device=queries.device)
+    check(lib().pqh_adc_tables_residual(ctx.ptr, pq.ptr, coarse.ptr, _ptr(queries), nq,
+                                        queries.stride(0), _ptr(probes), nprobe, _ptr(out)),
+          "pqh_adc_tables_residual")
+    return out
+
+
+def _range_search_out(range_ptr, k, out):
+    torch = _torch()
+    if out is not None:
+        return out
+    nq = range_ptr.numel() - 1
+    return (torch.empty((nq, k), dtype=torch.float32, device=range_ptr.device),
+            torch.empty((nq, k), dtype=torch.int64, device=range_ptr.device))
+
+
+def search_range_tables(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ranges,
+                        k: int, id_base: int = 0, out=None):
+    """search_ranges() with one table per range: lut float32 (nr, m, K), range r scored with
+    lut[r] (pqh_search_stream_range_tables) -- the probe search of a residual inverted file,
+    lut from adc_tables_residual.  The number of queries is range_ptr.numel() - 1."""
+    dist, ids = _range_search_out(range_ptr, k, out)
+    check(lib().pqh_search_stream_range_tables(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut),
+                                               range_ptr.numel() - 1, _ptr(range_ptr),
+                                               _ptr(ranges), ranges.shape[0], k, id_base,
+                                               _ptr(dist), _ptr(ids)),
+          "pqh_search_stream_range_tables")
+    return dist, ids
+
+
+def search_codes_range_tables(ctx: Context, codes, lut, range_ptr, ranges, k: int,
+                              id_base: int = 0, out=None):
+    """search_range_tables() over plain uint8 codes (n, m) (pqh_search_codes_range_tables)."""
+    dist, ids = _range_search_out(range_ptr, k, out)
+    check(lib().pqh_search_codes_range_tables(ctx.ptr, _ptr(codes), codes.shape[0],
+                                              codes.shape[1], lut.shape[2], _ptr(lut),
+                                              range_ptr.numel() - 1, _ptr(range_ptr),
+                                              _ptr(ranges), ranges.shape[0], k, id_base,
+                                              _ptr(dist), _ptr(ids)),
+          "pqh_search_codes_range_tables")
+    return dist, ids
+
+
 def ivf_layout(list_ids, nlist: int):
     """(perm, offsets) for storing rows list by list: perm is the stable order of the rows by
     list id (stream row s holds original row perm[s]), offsets int64 (nlist + 1,) with list l
@@ -725,6 +783,8 @@ class Coarse:
         check(lib().pqh_coarse_create(ctx.ptr, _ptr(c), self.nlist, self.d,
                                       ctypes.byref(self.ptr)), "pqh_coarse_create")
         ctx._retain()
+        # a device copy for torch (the fetch of a residual index adds a row's centroid back)
+        self.centroids = _torch().tensor(c, device=f"cuda:{ctx.device}")
 
     def assign(self, x, out=None, dist=None):
         """list ids int32 (n,) of the rows of x (device float32 (n, >= d)), the nearest
@@ -750,6 +810,25 @@ class Coarse:
         check(lib().pqh_ivf_layout(self.ctx.ptr, _ptr(list_ids), n, self.nlist, _ptr(perm),
                                    _ptr(offsets)), "pqh_ivf_layout")
         return perm, offsets
+
+    def residuals(self, x, list_ids, perm=None, out=None):
+        """out[s] = x[p] - centroid[list_ids[p]], p = perm[s] (perm None: p = s): the rows in
+        list order and their residuals in one pass (pqh_ivf_residuals).  list_ids: device int32
+        (n,) by caller row, as assign() returns them; perm: device int64 (n,) as layout()
+        returns it; out: float32 (n, >= d), only its first d columns written.  Async;
+        ivf_status reports a perm entry or a list id out of range (the row is then zeros)."""
+        torch = _torch()
+        n = x.shape[0]
+        if list_ids.dtype != torch.int32 or not list_ids.is_contiguous():
+            list_ids = list_ids.to(torch.int32).contiguous()
+        if perm is not None and not perm.is_contiguous():
+            perm = perm.contiguous()
+        if out is None:
+            out = torch.empty((n, self.d), dtype=torch.float32, device=x.device)
+        check(lib().pqh_ivf_residuals(self.ctx.ptr, self.ptr, _ptr(x), n, x.stride(0),
+                                      _ptr(list_ids), _ptr(perm), _ptr(out), out.stride(0)),
+              "pqh_ivf_residuals")
+        return out
 
     def probe(self, queries, nprobe: int, offsets, lists: bool = True):
         """(range_ptr, ranges, probes, probe_dist): for every query (device float32
@@ -783,8 +862,9 @@ class Coarse:
 
 
 def ivf_status(ctx: Context) -> None:
-    """raises PQH_ERR_ARG if a Coarse.layout / Coarse.probe since the last call met a bad value
-    (a list id outside [0, nlist), a reversed offsets pair); synchronises (pqh_ivf_status)"""
+    """raises PQH_ERR_ARG if a Coarse.layout / Coarse.probe / Coarse.residuals /
+    adc_tables_residual since the last call met a bad value (a list id outside [0, nlist), a
+    reversed offsets pair, a perm entry outside [0, n)); synchronises (pqh_ivf_status)"""
     st = lib().pqh_ivf_status(ctx.ptr)
     if st:
         raise PqhError(st, "pqh_ivf")
@@ -798,45 +878,91 @@ class IVF:
     The order of a result is (dist, stream row), that is (dist, list, caller row): rows of
     equal distance come list by list, NOT in caller-row order.
 
+    residual=True (IVFADC): the stream holds the PQ codes of x - centroid[list], every
+    (query, probed list) pair is scored with the table of query - centroid[list], and fetch()
+    adds the centroid back.  `pq` must then be trained on residuals, e.g.
+    kmeans_train(ctx, coarse.residuals(x, coarse.assign(x)), init, iters); a codebook trained
+    on x itself works but throws the gain away.  The tables of a search are
+    nq * nprobe * m * K * 4 bytes, so search() walks the queries in slabs whose tables stay
+    under `table_budget` bytes.
+
     Every stage is a call on the context's stream.  search() never waits for the device;
     build() waits where encode() does, once, for the stream's length."""
 
-    def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets):
+    table_budget = 256 << 20   # bytes of per-(query, list) tables a residual search holds at once
+
+    def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets, residual=False):
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
         self.perm, self.inv, self.offsets = perm, inv, offsets
+        self.residual = residual
 
     @classmethod
     def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
-              context: bool = True) -> "IVF":
+              context: bool = True, residual: bool = False) -> "IVF":
         """x: device float32 (n, d), d = coarse.d = pq.m * pq.dsub.  The stages: rows to
-        lists, layout, gather x[perm], pq.assign, histogram, Tables.build, encode."""
+        lists, layout, gather x[perm] (residual: coarse.residuals(x, lists, perm) in its
+        place), pq.assign, histogram, Tables.build, encode."""
         torch = _torch()
         if pq.k > 256 or pq.m > 16:
             raise PqhError(-4, "IVF.build: the search takes K <= 256 and m <= 16")
         if coarse.d != pq.m * pq.dsub or x.shape[1] != coarse.d:
             raise PqhError(-1, "IVF.build: x, the coarse centroids and the PQ disagree in d")
-        perm, offsets = coarse.layout(coarse.assign(x))
-        codes = pq.assign(x[perm], ctx=ctx)
+        lists = coarse.assign(x)
+        perm, offsets = coarse.layout(lists)
+        rows = coarse.residuals(x, lists, perm) if residual else x[perm]
+        codes = pq.assign(rows, ctx=ctx)
+        del rows
         counts = histogram(ctx, codes, pq.k, context)
         tables = Tables(ctx, pq.m, pq.k, context).build(counts)
         enc = encode(ctx, tables, codes, chunk_vectors=chunk_vectors)
         inv = torch.empty_like(perm)
         inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
-        return cls(ctx, pq, coarse, tables, enc, perm, inv, offsets)
+        return cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
 
     def search(self, queries, nprobe: int, k: int):
         """(dist, ids), each (nq, k): the k nearest rows by ADC distance among the rows of each
         query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1)."""
         torch = _torch()
+        if self.residual:
+            dist, rows = self._search_residual(queries, nprobe, k)
+            return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
         lut = adc_tables(self.ctx, self.pq, queries)
         range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False)
         dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k)
         return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
 
+    def _search_residual(self, queries, nprobe: int, k: int):
+        """(dist, stream rows): probe, one table per (query, list), the probe search with a
+        table per range -- slab by slab, the table buffer reused"""
+        torch = _torch()
+        nq = queries.shape[0]
+        per_query = nprobe * self.pq.m * self.pq.k * 4
+        slab = max(1, min(max(nq, 1), int(self.table_budget) // per_query))
+        dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+        rows = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+        lut = torch.empty((slab * nprobe, self.pq.m, self.pq.k), dtype=torch.float32,
+                          device=queries.device)
+        for s in range(0, nq, slab):
+            q = queries[s:s + slab]
+            range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True)
+            adc_tables_residual(self.ctx, self.pq, self.coarse, q, probes,
+                                out=lut[:q.shape[0] * nprobe])
+            search_range_tables(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
+                                out=(dist[s:s + slab], rows[s:s + slab]))
+        return dist, rows
+
     def fetch(self, ids, out=None):
         """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)), for
-        an exact re-rank (fetch through the inverse permutation)"""
-        return fetch(self.ctx, self.tables, self.pq, self.enc, self.inv[ids.reshape(-1)], out)
+        an exact re-rank (fetch through the inverse permutation; residual: the decoded
+        residual plus the centroid of the stream row's list, one fp32 add)"""
+        torch = _torch()
+        rows = self.inv[ids.reshape(-1)]
+        out = fetch(self.ctx, self.tables, self.pq, self.enc, rows, out)
+        if self.residual:
+            # (right=True passes over the empty lists that end where the row's list begins)
+            lists = torch.searchsorted(self.offsets[1:].contiguous(), rows, right=True)
+            out[:, :self.coarse.d] += self.coarse.centroids[lists]
+        return out
 
 
 def encode_status(ctx: Context) -> None:

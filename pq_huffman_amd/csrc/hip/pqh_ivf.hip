@@ -18,12 +18,19 @@
 //  ivf_layout     rocPRIM's stable radix_sort_pairs of (list id, row number) over
 //                 ceil(log2 nlist) bits, then one kernel: every offset by a binary search in
 //                 the sorted ids, and the check of the ids.
+// The residual form (the stream holds the PQ codes of x - c[list]):
+//  ivf_residual   out[s] = x[perm[s]] - c[list[perm[s]]], the gather into list order and the
+//                 subtract in one pass.  A half wave owns a row and reads 32 consecutive floats
+//                 (or float4s) of it a step, kResRows rows in flight; the centroids come from L2.
+//  adc_lut_residual  one workgroup per (query, probed list): the residual query q - c[l] staged
+//                 in LDS once, then adc_lut's sum for every one of the m * K entries.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "pqh_internal.h"
@@ -45,6 +52,7 @@ constexpr int kR = 8, kC = 8;       // a thread's block of sums
 constexpr int kStride = kTR + 4;    // floats between two dimensions of a staged tile (16-byte
                                     // aligned rows; kTR == kTC, so both tiles share it)
 static_assert(kTR == kTC && kTR == 16 * kR && kTC == 16 * kC, "256 threads as 16 x 16");
+constexpr int kResidualMaxD = PQH_ADC_RESIDUAL_MAX_D;   // the residual query in LDS: 64 KB
 
 __global__ void __launch_bounds__(256, 2)
 coarse_assign(const float* __restrict__ x, long long n, long long ld_x,
@@ -229,6 +237,114 @@ ivf_offsets(const int32_t* __restrict__ list, const uint32_t* __restrict__ sorte
     }
 }
 
+// A workgroup owns 8 * kResRows consecutive rows of the output, half wave h the rows
+// base + 8 u + h.  The kResRows rows' loads of a step are issued before the first subtract.  A row
+// whose perm entry or list id is out of range reads nothing and is stored as zeros.
+constexpr int kResRows = 4;
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+ivf_residual(const float* __restrict__ x, long long n, long long ld_x,
+             const int32_t* __restrict__ list, const long long* __restrict__ perm,
+             const float* __restrict__ cent, int nlist, int d, float* __restrict__ out,
+             long long ld_out, unsigned long long* __restrict__ err) {
+    using V = std::conditional_t<VEC, float4, float>;
+    constexpr int W = VEC ? 4 : 1;
+    const int hl = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const long long base = (long long)blockIdx.x * (8 * kResRows);
+    const float* xr[kResRows];
+    const float* cr[kResRows];
+    bool ok[kResRows];
+    bool bad = false;
+#pragma unroll
+    for (int u = 0; u < kResRows; ++u) {
+        const long long s = base + u * 8 + hw;
+        long long p = -1;
+        if (s < n) p = perm ? perm[s] : s;
+        bool good = p >= 0 && p < n;
+        int l = -1;
+        if (good) l = list[p];
+        good = good && l >= 0 && l < nlist;
+        bad = bad || (s < n && !good);
+        ok[u] = good;
+        xr[u] = x + (good ? p : 0) * ld_x;
+        cr[u] = cent + (long long)(good ? l : 0) * d;
+    }
+#pragma unroll 1
+    for (int j = hl * W; j < d; j += 32 * W) {
+        V xv[kResRows], cv[kResRows];
+#pragma unroll
+        for (int u = 0; u < kResRows; ++u) {
+            xv[u] = V{};
+            cv[u] = V{};
+            if (ok[u]) {
+                xv[u] = *reinterpret_cast<const V*>(xr[u] + j);
+                cv[u] = *reinterpret_cast<const V*>(cr[u] + j);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kResRows; ++u) {
+            const long long s = base + u * 8 + hw;
+            if (s < n) {
+                V r;
+                if constexpr (VEC)
+                    r = make_float4(xv[u].x - cv[u].x, xv[u].y - cv[u].y, xv[u].z - cv[u].z,
+                                    xv[u].w - cv[u].w);
+                else
+                    r = xv[u] - cv[u];
+                *reinterpret_cast<V*>(out + s * ld_out + j) = r;
+            }
+        }
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(err, 1ull);
+}
+
+// lut[o] for o = q * nprobe + p: the table of q - c[probes[o]] against the PQ centroids, the
+// sum of adc_lut (pqh_search.hip) with the residual read from LDS.  A list of -1 (the probe
+// selection's padding) or outside [0, nlist) (the error bit) gives a table of +inf.
+__global__ void __launch_bounds__(256)
+adc_lut_residual(const float* __restrict__ queries, long long ld_q, int nprobe,
+                 const long long* __restrict__ probes, const float* __restrict__ coarse,
+                 int nlist, const float* __restrict__ cent, int m, int k, int dsub, int vec,
+                 float* __restrict__ lut, unsigned long long* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) float res[];   // [m * dsub]
+    const int tid = threadIdx.x;
+    const long long o = blockIdx.x;
+    const long long l = probes[o];
+    const int per = m * k, d = m * dsub;
+    float* __restrict__ dst = lut + o * per;
+    if (l < 0 || l >= nlist) {   // (the same for every thread of the workgroup)
+        for (int e = tid; e < per; e += 256) dst[e] = INFINITY;
+        if (l != -1 && tid == 0) atomicOr(err, 1ull);
+        return;
+    }
+    const float* __restrict__ x = queries + (o / nprobe) * ld_q;
+    const float* __restrict__ cl = coarse + l * d;
+    for (int j = tid; j < d; j += 256) res[j] = x[j] - cl[j];
+    lds_barrier();
+    for (int e = tid; e < per; e += 256) {
+        const float* r = res + (e / k) * dsub;
+        const float* c = cent + (long long)e * dsub;
+        float acc = 0.f;
+        if (vec) {   // dsub a multiple of four and the centroids 16-byte aligned: the same sum
+            for (int j = 0; j < dsub; j += 4) {
+                const float4 cv = *reinterpret_cast<const float4*>(c + j);
+                const float t0 = r[j] - cv.x, t1 = r[j + 1] - cv.y, t2 = r[j + 2] - cv.z,
+                            t3 = r[j + 3] - cv.w;
+                acc = acc + t0 * t0;
+                acc = acc + t1 * t1;
+                acc = acc + t2 * t2;
+                acc = acc + t3 * t3;
+            }
+        } else {
+            for (int j = 0; j < dsub; ++j) {
+                const float t = r[j] - c[j];
+                acc = acc + t * t;
+            }
+        }
+        dst[e] = acc;
+    }
+}
+
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -349,6 +465,50 @@ int pqh_coarse_probe(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_quer
     hipLaunchKernelGGL(coarse_probe, dim3((unsigned)nq), dim3(64, kProbeWaves), 0, ctx->stream,
                        d_queries, nq, ld_q, cq->d_cent_t, cq->nlist, cq->d, nprobe, d_offsets,
                        d_range_ptr, d_ranges, d_probes, d_probe_dist, ctx->d_diag + kDiagIvf);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int pqh_ivf_residuals(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
+                      long long ld_x, const int32_t* d_list, const long long* d_perm, float* d_out,
+                      long long ld_out) {
+    if (!ctx) return pqh_no_ctx_status();
+    if (!cq || n < 0 || ld_x < cq->d || ld_out < cq->d || (n > 0 && (!d_x || !d_list || !d_out)))
+        return PQH_ERR_ARG;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (n == 0) return PQH_OK;
+    const long long blocks = (n + 8 * kResRows - 1) / (8 * kResRows);
+    if (blocks > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    // float4 steps where every row of x, out and the centroids starts on 16 bytes
+    const bool vec = cq->d % 4 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 &&
+                     !((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_out) |
+                        reinterpret_cast<uintptr_t>(cq->d_cent)) & 15u);
+    hipLaunchKernelGGL(vec ? ivf_residual<true> : ivf_residual<false>, dim3((unsigned)blocks),
+                       dim3(256), 0, ctx->stream, d_x, n, ld_x, d_list, d_perm, cq->d_cent,
+                       cq->nlist, cq->d, d_out, ld_out, ctx->d_diag + kDiagIvf);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int pqh_adc_tables_residual(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse_t* cq,
+                            const float* d_queries, long long nq, long long ld_q,
+                            const long long* d_probes, int nprobe, float* d_lut) {
+    if (!ctx) return pqh_no_ctx_status();
+    int m = 0, k = 0, dsub = 0;
+    const float* d_cent = nullptr;
+    if (pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || !cq || (long long)m * dsub != cq->d || nq < 0 ||
+        nprobe < 1 || ld_q < cq->d || (nq > 0 && (!d_queries || !d_probes || !d_lut)))
+        return PQH_ERR_ARG;
+    if (k > 256 || cq->d > kResidualMaxD || nq * nprobe > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (nq == 0) return PQH_OK;
+    const int vec = dsub % 4 == 0 && !(reinterpret_cast<uintptr_t>(d_cent) & 15u);
+    hipLaunchKernelGGL(adc_lut_residual, dim3((unsigned)(nq * nprobe)), dim3(256),
+                       (size_t)cq->d * 4, ctx->stream, d_queries, ld_q, nprobe, d_probes,
+                       cq->d_cent, cq->nlist, d_cent, m, k, dsub, vec, d_lut,
+                       ctx->d_diag + kDiagIvf);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
 }

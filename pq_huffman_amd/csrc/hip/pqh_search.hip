@@ -13,6 +13,9 @@
 //              RG = 1 (the probe search): every query has its own row ranges, so a workgroup
 //              holds one query's table (QB = 1) and its steps are those of adc_plan: a step
 //              is up to L chunks of one range, and only the rows inside the range are offered.
+//              RT = 1 (beside RG): one table per range, not per query.  Every wave keeps the
+//              table of its current range in LDS of its own, reloads it when its step's range
+//              changes, and takes a contiguous share of the workgroup's steps.
 //  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
 //  adc_merge   one workgroup per query: every scan workgroup's list through the same list code
 //              (pqh_topk_dev.h, shared with the probe selection of pqh_ivf.hip).
@@ -34,6 +37,7 @@ constexpr int kLdsBytes = 160 * 1024;
 constexpr int kCodesRowsPerLane = 4;       // SRC = 1: a wave stages 64 * 4 rows per step
 constexpr int kRangeWaves = 4;             // the probe search: waves per workgroup, and how many
 constexpr int kRangeFill = 4;              // times over its workgroups fill the compute units
+constexpr int kRangeTableWaves = 2;        // the same with a table per range (and per wave)
 
 __global__ void __launch_bounds__(256)
 adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
@@ -76,7 +80,7 @@ struct ScanArgs {
                                 // are too many for the stage
     long long steps;            // ceil(chunks / L)
     int stage_bytes, win_words; // per wave
-    const float* lut;           // [nq][m][k]
+    const float* lut;           // [nq][m][k]; RT: [nr][m][k]
     long long nq;
     int top_k;
     float* part_d;              // [nq][groups][top_k]: one list per workgroup and query
@@ -141,10 +145,14 @@ adc_plan(const long long* __restrict__ ranges, long long nr, long long n, int C,
     if (bad) atomicOr(err, 2ull);
 }
 
-template <int SRC, int NW, bool CTX, int QB, bool RG = false>
+// the bytes of one wave's table in the RT form (the stages after the tables stay 16-byte aligned)
+__host__ __device__ __forceinline__ int range_table_bytes(int mk) { return (mk * 4 + 15) & ~15; }
+
+template <int SRC, int NW, bool CTX, int QB, bool RG = false, bool RT = false>
 __global__ void __launch_bounds__(64 * kScanWavesMax)
 adc_scan(const ScanArgs a) {
     static_assert(RG == (QB == 1), "one query per workgroup is the probe search's form");
+    static_assert(!RT || RG, "a table per range is a form of the probe search");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int lane = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
@@ -153,15 +161,18 @@ adc_scan(const ScanArgs a) {
     const int k = a.k;
     const int C = a.C;
     const int mk = m * k;
-    float* lut_lds = reinterpret_cast<float*>(lds);   // [m][k][QB]
+    // [m][k][QB]; RT: the wave's own [m][k], the waves' tables side by side before the stages
+    float* lut_lds = reinterpret_cast<float*>(lds + (RT ? (size_t)wave * range_table_bytes(mk) : 0));
     const int per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
-    unsigned char* stage = reinterpret_cast<unsigned char*>(lds) + (size_t)mk * QB * 4 +
+    unsigned char* stage = reinterpret_cast<unsigned char*>(lds) +
+                           (RT ? (size_t)waves * range_table_bytes(mk) : (size_t)mk * QB * 4) +
                            (size_t)wave * per_wave;
     uint32_t* win = reinterpret_cast<uint32_t*>(stage + a.stage_bytes);
 
     // the batch's tables, the query innermost: one 16-byte read is four queries' entries
+    // (RT: nothing yet, a wave loads the table of a range when it comes to it)
     const long long q0 = (long long)blockIdx.x * QB;
-    for (int e = wave * 64 + lane; e < mk; e += waves * 64) {
+    for (int e = wave * 64 + lane; !RT && e < mk; e += waves * 64) {
         float v[QB];
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) v[qq] = q0 + qq < a.nq ? a.lut[(q0 + qq) * mk + e] : 0.f;
@@ -200,9 +211,18 @@ adc_scan(const ScanArgs a) {
     // this workgroup's span of steps; its waves take them in turn
     const long long g_lo = (long long)blockIdx.y * steps / gridDim.y;
     const long long g_hi = ((long long)blockIdx.y + 1) * steps / gridDim.y;
+    // RT: a contiguous share for every wave instead.  A range's steps are neighbours, so its
+    // table is loaded by the waves that share it, not by every wave of the workgroup (the
+    // result is the same: the order is total).  In either form the trip counts differ from
+    // wave to wave, so nothing in the loop may wait for another wave: the table is the wave's
+    // own.  (g_inc an int: as a long long it changes the code of the other forms)
+    const long long g_first = RT ? g_lo + (long long)wave * (g_hi - g_lo) / waves : g_lo + wave;
+    const long long g_end = RT ? g_lo + ((long long)wave + 1) * (g_hi - g_lo) / waves : g_hi;
+    const int g_inc = RT ? 1 : waves;
+    long long r_loaded = -1;   // RT: the range whose table the wave holds
     long long r_cur = r_lo;   // RG: the range of the wave's last step (its steps ascend)
 #pragma unroll 1
-    for (long long g = g_lo + wave; g < g_hi; g += waves) {
+    for (long long g = g_first; g < g_end; g += g_inc) {
         long long j0 = g * a.L;
         long long jn = min(chunks - j0, (long long)a.L);
         long long lo = 0, hi = 0;   // RG: the step's rows inside its range are [lo, hi)
@@ -223,6 +243,21 @@ adc_scan(const ScanArgs a) {
             jn = min((first + count - 1) / C + 1 - j0, (long long)a.L);
             lo = max(first, j0 * C);
             hi = min(first + count, (j0 + jn) * C);
+            if constexpr (RT) {
+                // (the reads of the table before are done: the wave_lds_sync that ends a step;
+                // the new one is complete at the wave_lds_sync before the scoring)
+                if (r_cur != r_loaded) {
+                    const float* src = a.lut + r_cur * mk;
+                    if (!(mk & 3) && !(reinterpret_cast<uintptr_t>(a.lut) & 15u)) {
+                        for (int e = lane; e < mk / 4; e += 64)
+                            reinterpret_cast<float4*>(lut_lds)[e] =
+                                reinterpret_cast<const float4*>(src)[e];
+                    } else {
+                        for (int e = lane; e < mk; e += 64) lut_lds[e] = src[e];
+                    }
+                    r_loaded = r_cur;
+                }
+            }
         }
         const long long row0 = j0 * C;
         const int nrows = (int)(min(a.n, (j0 + (RG ? jn : (long long)a.L)) * C) - row0);
@@ -471,9 +506,10 @@ int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long lon
 
 // the scan and the merge; a.C, a.n, a.m, a.k and the source are set by the caller, nw = the
 // row's u64 words (0: per part).  rg: the probe search (a.range_ptr, a.ranges and a.nr set):
-// the plan first, then one query per workgroup.
+// the plan first, then one query per workgroup.  rt (with rg): a.lut holds one table per
+// range; the stage, the window and so the plan are those of rg, only the waves may be fewer.
 int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long id_base,
-                float* d_dist, long long* d_ids, bool rg = false) {
+                float* d_dist, long long* d_ids, bool rg = false, bool rt = false) {
     if (a.nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
     const int m = a.m, k = a.k;
     // the batch's tables: at most 64 KB; 16-part rows keep to four queries (eight running
@@ -499,7 +535,12 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         if (a.stage_bytes + (a.win_words + 4) * 4 > budget) a.win_words = 0;
     }
     const long long per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
-    int fit = floor_pow2(std::min<long long>(kScanWavesMax, budget / per_wave));
+    // rt: every wave has a table of its own beside its stage (one of them is in the budget,
+    // so one wave always fits)
+    const long long wave_table = rt ? range_table_bytes(m * k) : 0;
+    if (per_wave + wave_table > kLdsBytes) return PQH_ERR_UNSUPPORTED;   // (rounding, at most)
+    int fit = floor_pow2(std::min<long long>(
+        kScanWavesMax, rt ? kLdsBytes / (per_wave + wave_table) : budget / per_wave));
     a.steps = (chunks + a.L - 1) / a.L;
     const long long batches = (a.nq + qb - 1) / qb;
     // one workgroup per compute unit over all query batches (a workgroup's tables take most
@@ -511,11 +552,16 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         // leaves room for several workgroups of kRangeWaves waves on a compute unit, and
         // nq * groups workgroups fill the compute units kRangeFill times over; a query has at
         // most the stream's steps unless its ranges overlap.
-        fit = std::min(fit, kRangeWaves);
+        fit = std::min(fit, rt ? kRangeTableWaves : kRangeWaves);
+        // rt: the waves' tables are most of the LDS, which holds twelve waves a compute unit at
+        // m = 8 where the one-table form holds twenty.  The grid is what is resident at once
+        // and no more (rounded down: a workgroup more would wait for a whole round of the
+        // others), in workgroups of two waves so that the rounding costs little
+        long long wgs = (kRangeFill * (long long)ctx->num_cus + a.nq - 1) / a.nq;
+        if (rt)
+            wgs = kLdsBytes / (fit * (per_wave + wave_table)) * (long long)ctx->num_cus / a.nq;
         if (ctx->tune_search_groups <= 0)
-            groups = std::min<long long>(
-                (kRangeFill * (long long)ctx->num_cus + a.nq - 1) / a.nq,
-                (a.steps + fit - 1) / fit);
+            groups = std::min<long long>(wgs, (a.steps + fit - 1) / fit);
         groups = std::min<long long>(std::max<long long>(groups, 1), 65535);
     } else {
         groups = std::min<long long>(std::min<long long>(groups, a.steps), 65535);
@@ -538,11 +584,13 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         a.plan = plan;
     }
     // (the end of the kernel exchanges the waves' lists, 12 bytes an entry, through the same LDS)
-    const size_t lds = std::max<size_t>((size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
-                                        (size_t)waves * qb * 64 * 12);
-    auto launch = [&](auto s, auto w, auto c, auto q) -> int {
+    const size_t lds = std::max<size_t>(
+        rt ? (size_t)waves * (size_t)(wave_table + per_wave)
+           : (size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
+        (size_t)waves * qb * 64 * 12);
+    auto launch = [&](auto s, auto w, auto c, auto q, auto tb) -> int {
         auto* fn = adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
-                            decltype(q)::value, decltype(q)::value == 1>;
+                            decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value>;
         if (lds > 64 * 1024)
             PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -551,10 +599,11 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         return PQH_OK;
     };
     auto with_qb = [&](auto s, auto w, auto c) -> int {
-        if (rg) return launch(s, w, c, Int<1>());
+        if (rt) return launch(s, w, c, Int<1>(), std::true_type());
+        if (rg) return launch(s, w, c, Int<1>(), std::false_type());
         if constexpr (decltype(w)::value != 2)
-            if (qb == 8) return launch(s, w, c, Int<8>());
-        return launch(s, w, c, Int<4>());
+            if (qb == 8) return launch(s, w, c, Int<8>(), std::false_type());
+        return launch(s, w, c, Int<4>(), std::false_type());
     };
     auto with_nw = [&](auto s, auto c) -> int {
         return nw == 1 ? with_qb(s, Int<1>(), c) : nw == 2 ? with_qb(s, Int<2>(), c)
@@ -595,9 +644,10 @@ struct Probe {
     const long long* range_ptr;
     const long long* ranges;
     long long nr;
+    bool tables = false;   // the *_range_tables calls: d_lut is [nr][m][K]
 };
 
-// pqh_search_stream (pr = null) and pqh_search_stream_ranges
+// pqh_search_stream (pr = null), pqh_search_stream_ranges and pqh_search_stream_range_tables
 int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
                   unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
                   const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
@@ -634,10 +684,10 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
     // rows of whole u64 words with the chunk contexts readable as such: the packed walk
     const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
     return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, id_base, d_dist, d_ids,
-                       pr != nullptr);
+                       pr != nullptr, pr && pr->tables);
 }
 
-// pqh_search_codes (pr = null) and pqh_search_codes_ranges
+// pqh_search_codes (pr = null), pqh_search_codes_ranges and pqh_search_codes_range_tables
 int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                  const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
                  float* d_dist, long long* d_ids) {
@@ -661,7 +711,7 @@ int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
     a.top_k = top_k;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
     return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids,
-                       pr != nullptr);
+                       pr != nullptr, pr && pr->tables);
 }
 
 }  // namespace
@@ -721,6 +771,28 @@ int pqh_search_codes_ranges(pqh_ctx_t* ctx, const void* d_codes, long long n, in
                             const long long* d_ranges, long long nr, int top_k, long long id_base,
                             float* d_dist, long long* d_ids) {
     const Probe pr{d_range_ptr, d_ranges, nr};
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, &pr, top_k, id_base, d_dist, d_ids);
+}
+
+int pqh_search_stream_range_tables(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                   const unsigned char* d_stream, unsigned long long stream_bytes,
+                                   long long n, int raw_first, int chunk_vectors,
+                                   const unsigned long long* d_chunk_offsets,
+                                   const void* d_chunk_prev, const float* d_lut, long long nq,
+                                   const long long* d_range_ptr, const long long* d_ranges,
+                                   long long nr, int top_k, long long id_base, float* d_dist,
+                                   long long* d_ids) {
+    const Probe pr{d_range_ptr, d_ranges, nr, true};
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, &pr, top_k, id_base, d_dist,
+                         d_ids);
+}
+
+int pqh_search_codes_range_tables(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                                  const float* d_lut, long long nq, const long long* d_range_ptr,
+                                  const long long* d_ranges, long long nr, int top_k,
+                                  long long id_base, float* d_dist, long long* d_ids) {
+    const Probe pr{d_range_ptr, d_ranges, nr, true};
     return search_codes(ctx, d_codes, n, m, k, d_lut, nq, &pr, top_k, id_base, d_dist, d_ids);
 }
 
