@@ -441,6 +441,47 @@ int pqh_search_codes_range_tables(pqh_ctx_t* ctx, const void* d_codes, long long
                                   long long nr, int top_k, long long id_base, float* d_dist,
                                   long long* d_ids);
 
+/* The probe search in list-major order: the same result, but a list that several queries
+ * probe is decoded once per batch of them instead of once per query -- the schedule for many
+ * queries, when nq * nprobe exceeds nlist and the same lists are probed again and again.
+ * The probe list is given as pqh_coarse_probe writes it: d_offsets int64 [nlist + 1] (list l is
+ * the stream rows [d_offsets[l], d_offsets[l + 1])) and d_probes int64 [nq][nprobe], -1 = none.
+ * tables_per_probe == 0: d_lut is float [nq][m][K] and the result is
+ * pqh_search_stream_ranges' for the ranges of these probes (range q * nprobe + p = list
+ * d_probes[q][p]); tables_per_probe != 0: d_lut is float [nq * nprobe][m][K], pair (q, p)
+ * scored with table q * nprobe + p, and the result is pqh_search_stream_range_tables' --
+ * either way id for id and bit for bit, since the order (dist, stream row) is total and dist
+ * the same sum.  A list that appears twice in a query's probes offers its rows twice (each
+ * time with its own table, if there is one per probe); a probe of -1 contributes nothing and
+ * its table is never read, nor is that of a list without rows.
+ * On the device the probes are turned round (for every list the pairs that probe it), cut
+ * into work units of a list and up to 8 pairs (4 when m > 8), and a unit's workgroups decode
+ * the list's chunks once and score every row against the unit's tables.  Chunks under no
+ * probed list are neither read nor walked.
+ * Bad device data is reported by PQH_ERR_ARG from pqh_decode_status (PQH_ERR_CORRUPT takes
+ * precedence) and contributes no rows: a probe below -1 or >= nlist, a probed list whose
+ * offsets are not 0 <= d_offsets[l] <= d_offsets[l + 1] <= n.  Decode errors are
+ * pqh_search_stream_ranges' for the chunks that are walked.
+ * PQH_ERR_ARG at once: the cases of pqh_search_stream, nlist < 1, nprobe < 1, a null
+ * d_offsets or d_probes when nq > 0.  PQH_ERR_UNSUPPORTED: those of pqh_search_stream,
+ * nq * nprobe >= 2^31, nlist >= 2^31.  nq == 0 launches nothing; n == 0 fills the outputs with
+ * the padding.  The call never waits for the device.
+ * Scratch: 12 bytes * nq * nprobe * top_k per workgroup row of the scan grid, and
+ * 4 * (nq * nprobe + nlist) + 24 * min(nq * nprobe, nlist + nq * nprobe / 4) bytes. */
+int pqh_search_stream_lists(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                            unsigned long long stream_bytes, long long n, int raw_first,
+                            int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                            const void* d_chunk_prev, const long long* d_offsets /* [nlist + 1] */,
+                            long long nlist, const long long* d_probes /* [nq][nprobe] */,
+                            long long nq, int nprobe, const float* d_lut, int tables_per_probe,
+                            int top_k, long long id_base, float* d_dist, long long* d_ids);
+
+/* The same over plain row-major u8 codes [n][m]. */
+int pqh_search_codes_lists(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                           const long long* d_offsets, long long nlist, const long long* d_probes,
+                           long long nq, int nprobe, const float* d_lut, int tables_per_probe,
+                           int top_k, long long id_base, float* d_dist, long long* d_ids);
+
 /* ---- inverted file: coarse quantizer, list layout, probe selection ---------------------
  * The front end of the probe search: rows are assigned to the nearest of nlist coarse
  * centroids (full d-dimensional vectors), stored list by list, and a query probes the nprobe

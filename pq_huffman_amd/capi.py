@@ -168,6 +168,9 @@ SIGNATURES = [
     ("pqh_search_stream_range_tables", I,
      [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, LL, P, P]),
     ("pqh_search_codes_range_tables", I, [P, P, LL, I, I, P, LL, P, P, LL, I, LL, P, P]),
+    ("pqh_search_stream_lists", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, LL, I, P, I, I, LL, P, P]),
+    ("pqh_search_codes_lists", I, [P, P, LL, I, I, P, LL, P, LL, I, P, I, I, LL, P, P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

@@ -18,6 +18,8 @@ calls on device-resident data:
     search_range_tables  the probe search with one table per (query, list): the residual form
                          of the inverted file (Coarse.residuals, adc_tables_residual,
                          IVF.build(residual=True))
+    search_lists         the probe search in list-major order: a list decoded once per batch of
+                         the queries that probe it (IVF.search(schedule="list"))
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
@@ -737,6 +739,54 @@ def search_codes_range_tables(ctx: Context, codes, lut, range_ptr, ranges, k: in
     return dist, ids
 
 
+def _lists_args(lut, offsets, probes, k, out):
+    """(nlist, probes, nq, nprobe, tables_per_probe, dist, ids) of the list-major calls: the
+    table form from lut.shape[0], nq for a table per query, nq * nprobe for one per pair"""
+    torch = _torch()
+    nq, nprobe = probes.shape
+    if lut.shape[0] == nq * nprobe and nprobe > 1:
+        per_probe = 1
+    elif lut.shape[0] == nq:
+        per_probe = 0
+    else:
+        raise PqhError(-1, f"search_lists: {lut.shape[0]} tables for {nq} queries of {nprobe} probes")
+    if not probes.is_contiguous():
+        probes = probes.contiguous()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=probes.device),
+               torch.empty((nq, k), dtype=torch.int64, device=probes.device))
+    return offsets.numel() - 1, probes, nq, nprobe, per_probe, out[0], out[1]
+
+
+def search_lists(ctx: Context, tables: Tables, enc: Encoded, lut, offsets, probes, k: int,
+                 id_base: int = 0, out=None):
+    """the probe search in list-major order (pqh_search_stream_lists): the result of
+    search_ranges (lut float32 (nq, m, K)) or search_range_tables (lut (nq * nprobe, m, K)) on
+    probe_ranges(offsets, probes), bit for bit, but a list probed by several queries is decoded
+    once per batch of eight of them (four when m > 8) -- the schedule for many queries.
+    offsets: device int64 (nlist + 1,) as ivf_layout gives them; probes: device int64
+    (nq, nprobe), -1 = none.  Async; decode_status reports a corrupt chunk that was walked
+    (PQH_ERR_CORRUPT) or a probe outside [-1, nlist) or a bad offsets pair of a probed list
+    (PQH_ERR_ARG, the probe skipped)."""
+    nlist, probes, nq, nprobe, per_probe, dist, ids = _lists_args(lut, offsets, probes, k, out)
+    check(lib().pqh_search_stream_lists(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(offsets),
+                                        nlist, _ptr(probes), nq, nprobe, _ptr(lut), per_probe, k,
+                                        id_base, _ptr(dist), _ptr(ids)),
+          "pqh_search_stream_lists")
+    return dist, ids
+
+
+def search_codes_lists(ctx: Context, codes, lut, offsets, probes, k: int, id_base: int = 0,
+                       out=None):
+    """search_lists() over plain uint8 codes (n, m) (pqh_search_codes_lists)."""
+    nlist, probes, nq, nprobe, per_probe, dist, ids = _lists_args(lut, offsets, probes, k, out)
+    check(lib().pqh_search_codes_lists(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1],
+                                       lut.shape[2], _ptr(offsets), nlist, _ptr(probes), nq,
+                                       nprobe, _ptr(lut), per_probe, k, id_base, _ptr(dist),
+                                       _ptr(ids)), "pqh_search_codes_lists")
+    return dist, ids
+
+
 def ivf_layout(list_ids, nlist: int):
     """(perm, offsets) for storing rows list by list: perm is the stable order of the rows by
     list id (stream row s holds original row perm[s]), offsets int64 (nlist + 1,) with list l
@@ -890,6 +940,12 @@ class IVF:
     build() waits where encode() does, once, for the stream's length."""
 
     table_budget = 256 << 20   # bytes of per-(query, list) tables a residual search holds at once
+    # schedule="auto": list-major from nq * nprobe >= list_major_ratio * nlist on.  Measured at
+    # 125M rows in 1,024 lists (DESIGN.md section 4.5.6): in chunks of 4 rows the list form is
+    # ahead from a ratio of 1 on (1.35x, 3.2x at 4, 5x at 8), in chunks of 64 from 4 on (0.68x at
+    # 1, 1.6x at 4); 4.0 is the first point ahead on both.  With lists of under a thousand rows
+    # the query-major form stays ahead up to a ratio of 32.
+    list_major_ratio = 4.0
 
     def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets, residual=False):
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
@@ -919,21 +975,33 @@ class IVF:
         inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
         return cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
 
-    def search(self, queries, nprobe: int, k: int):
+    def search(self, queries, nprobe: int, k: int, schedule: str = "query"):
         """(dist, ids), each (nq, k): the k nearest rows by ADC distance among the rows of each
-        query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1)."""
+        query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1).
+        schedule: "query" decodes a list once for every query that probes it (search_ranges),
+        "list" once per batch of the queries that probe it (search_lists), "auto" takes "list"
+        from nq * nprobe >= list_major_ratio * nlist on; the result is the same bits."""
         torch = _torch()
+        if schedule not in ("query", "list", "auto"):
+            raise PqhError(-1, f"IVF.search: schedule {schedule!r}")
+        by_list = schedule == "list" or (
+            schedule == "auto" and
+            queries.shape[0] * nprobe >= self.list_major_ratio * self.coarse.nlist)
         if self.residual:
-            dist, rows = self._search_residual(queries, nprobe, k)
+            dist, rows = self._search_residual(queries, nprobe, k, by_list)
             return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
         lut = adc_tables(self.ctx, self.pq, queries)
-        range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False)
-        dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k)
+        range_ptr, ranges, probes, _ = self.coarse.probe(queries, nprobe, self.offsets,
+                                                         lists=by_list)
+        if by_list:
+            dist, rows = search_lists(self.ctx, self.tables, self.enc, lut, self.offsets, probes, k)
+        else:
+            dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k)
         return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
 
-    def _search_residual(self, queries, nprobe: int, k: int):
+    def _search_residual(self, queries, nprobe: int, k: int, by_list: bool = False):
         """(dist, stream rows): probe, one table per (query, list), the probe search with a
-        table per range -- slab by slab, the table buffer reused"""
+        table per range (by_list: per pair, list-major) -- slab by slab, the table buffer reused"""
         torch = _torch()
         nq = queries.shape[0]
         per_query = nprobe * self.pq.m * self.pq.k * 4
@@ -947,8 +1015,13 @@ class IVF:
             range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True)
             adc_tables_residual(self.ctx, self.pq, self.coarse, q, probes,
                                 out=lut[:q.shape[0] * nprobe])
-            search_range_tables(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
-                                out=(dist[s:s + slab], rows[s:s + slab]))
+            out = (dist[s:s + slab], rows[s:s + slab])
+            if by_list:
+                search_lists(self.ctx, self.tables, self.enc, lut[:q.shape[0] * nprobe],
+                             self.offsets, probes, k, out=out)
+            else:
+                search_range_tables(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
+                                    out=out)
         return dist, rows
 
     def fetch(self, ids, out=None):

@@ -16,7 +16,12 @@
 //              RT = 1 (beside RG): one table per range, not per query.  Every wave keeps the
 //              table of its current range in LDS of its own, reloads it when its step's range
 //              changes, and takes a contiguous share of the workgroup's steps.
+//              LM = 1 (the list-major probe search, QB = 8 or 4): a workgroup holds a list
+//              and the tables of up to QB of the (query, probe) pairs that probe it, so a step
+//              of the list is decoded once for all of them; its lists go to the pairs' slots.
 //  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
+//  lists_*     the probe list turned round for LM: the pairs of every list in CSR form
+//              (count, scan, fill), cut into work units of up to QB pairs.
 //  adc_merge   one workgroup per query: every scan workgroup's list through the same list code
 //              (pqh_topk_dev.h, shared with the probe selection of pqh_ivf.hip).
 //
@@ -72,6 +77,8 @@ struct ScanArgs {
     const void* chunk_prev;
     DecTabs T;
     int raw_first;
+    int nprobe;                 // LM (in what was padding, as pair_tables: the struct keeps its
+                                // layout, and the other forms' code with it)
     const unsigned char* codes; // SRC = 1: rows [n][m]
     long long n;
     int m, k;
@@ -80,18 +87,32 @@ struct ScanArgs {
                                 // are too many for the stage
     long long steps;            // ceil(chunks / L)
     int stage_bytes, win_words; // per wave
-    const float* lut;           // [nq][m][k]; RT: [nr][m][k]
+    const float* lut;           // [nq][m][k]; RT: [nr][m][k]; LM: either, by pair_tables
     long long nq;
     int top_k;
+    int pair_tables;            // LM: lut holds one table per pair, not one per query
     float* part_d;              // [nq][groups][top_k]: one list per workgroup and query
-    long long* part_id;
+    long long* part_id;         // (LM: [nq * nprobe][groups][top_k], per pair and workgroup)
     unsigned long long* err;
-    // RG: the probe list in CSR form (device data, checked on the device) and adc_plan's prefix
-    const long long* range_ptr; // [nq + 1]
-    const long long* ranges;    // [nr][2]: first row, count
-    long long nr;
-    const long long* plan;      // [nr + 1]
+    union {
+        // RG: the probe list in CSR form (device data, checked on the device) and adc_plan's
+        // prefix
+        struct {
+            const long long* range_ptr; // [nq + 1]
+            const long long* ranges;    // [nr][2]: first row, count
+            long long nr;
+            const long long* plan;      // [nr + 1]
+        };
+        // LM: the lists' rows, and lists_plan's work units with the pairs behind them
+        struct {
+            const long long* offsets;   // [nlist + 1]
+            const long long* units;     // [unit bound][3]: list, first entry of pairs, entries
+            const long long* nunits;    // how many of them there are
+            const int* pairs;           // the pairs q * nprobe + p of every list, list by list
+        };
+    };
 };
+static_assert(sizeof(ScanArgs) == sizeof(DecTabs) + 168, "LM's fields must not move the others");
 
 // The chunks of a good range: [first / C, (first + count - 1) / C + 1); a range is good when
 // 0 <= first <= n and 0 <= count <= n - first (no sum that could overflow).
@@ -148,11 +169,126 @@ adc_plan(const long long* __restrict__ ranges, long long nr, long long n, int C,
 // the bytes of one wave's table in the RT form (the stages after the tables stay 16-byte aligned)
 __host__ __device__ __forceinline__ int range_table_bytes(int mk) { return (mk * 4 + 15) & ~15; }
 
-template <int SRC, int NW, bool CTX, int QB, bool RG = false, bool RT = false>
+// ------------------------------------------------------------------- the list-major plan
+// The probe list [nq][nprobe] turned round: for every list the pairs q * nprobe + p that probe
+// it, and the work units of the scan, a list and up to qb of its pairs each.  A pair takes
+// part when its list id is in [0, nlist) and the list's offsets are a good range with rows;
+// every other pair has no unit, so its partial lists are filled with the padding here (no
+// memset of the buffer), and a list id that is neither -1 nor in [0, nlist) or a bad offsets
+// pair sets error bit 2.  Four small launches: the counts zeroed, counted, scanned into units,
+// and the pairs filled in (in any order: a pair's result does not depend on its batch).
+struct ListArgs {
+    const long long* offsets;   // [nlist + 1]
+    long long nlist;
+    const long long* probes;    // [pairs], -1 = none
+    long long npairs;
+    long long n;
+    int qb;
+    long long pad;              // groups * top_k: a pair's entries of the partial lists
+    int* cnt;                   // [nlist]: the list's pairs, then the fill's cursor
+    long long* units;
+    long long* nunits;
+    int* pairs;
+    float* part_d;
+    long long* part_id;
+    unsigned long long* err;
+};
+
+// the list of pair i if it takes part, else -1 (*bad: a value that is reported)
+__device__ __forceinline__ long long list_of_pair(const ListArgs& a, long long i, bool* bad) {
+    const long long l = a.probes[i];
+    *bad = false;
+    if (l < 0 || l >= a.nlist) {
+        *bad = l != -1;
+        return -1;
+    }
+    const long long first = a.offsets[l], next = a.offsets[l + 1];
+    if (first < 0 || next < first || !range_ok(first, next - first, a.n)) {
+        *bad = true;
+        return -1;
+    }
+    return next > first ? l : -1;
+}
+
+__global__ void __launch_bounds__(256) lists_zero(const ListArgs a) {
+    const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (l < a.nlist) a.cnt[l] = 0;
+}
+
+__global__ void __launch_bounds__(256) lists_count(const ListArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.npairs) return;
+    bool bad;
+    const long long l = list_of_pair(a, i, &bad);
+    if (l >= 0) {
+        atomicAdd(a.cnt + l, 1);
+    } else {
+        for (long long e = i * a.pad; e < (i + 1) * a.pad; ++e) {
+            a.part_d[e] = INFINITY;
+            a.part_id[e] = -1ll;
+        }
+    }
+    if (bad) atomicOr(a.err, 2ull);
+}
+
+// One workgroup, 1,024 lists a round as adc_plan: the exclusive prefixes of the lists' pairs
+// and of their units, cnt[l] left as the first entry of the list's pairs, and every list's
+// units written by its thread.
+__global__ void __launch_bounds__(64 * kPlanWaves) lists_plan(const ListArgs a) {
+    __shared__ int wsum[2][kPlanWaves];
+    const int lane = threadIdx.x;
+    const int wave = threadIdx.y;
+    int carry_p = 0, carry_u = 0;   // (fewer than 2^31 pairs, so as many units at the most)
+    for (long long base = 0; base < a.nlist; base += 64 * kPlanWaves) {
+        const long long l = base + wave * 64 + lane;
+        const int c = l < a.nlist ? a.cnt[l] : 0;
+        const int s = (c + a.qb - 1) / a.qb;
+        int inc_p = c, inc_u = s;   // the wave's inclusive prefixes
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int tp = __shfl_up(inc_p, d), tu = __shfl_up(inc_u, d);
+            inc_p += lane >= d ? tp : 0;
+            inc_u += lane >= d ? tu : 0;
+        }
+        if (lane == 63) wsum[0][wave] = inc_p, wsum[1][wave] = inc_u;
+        lds_barrier();
+        int p0 = carry_p + inc_p - c, u0 = carry_u + inc_u - s;
+#pragma unroll 1
+        for (int w = 0; w < kPlanWaves; ++w) {
+            p0 += w < wave ? wsum[0][w] : 0;
+            u0 += w < wave ? wsum[1][w] : 0;
+            carry_p += wsum[0][w];
+            carry_u += wsum[1][w];
+        }
+        if (l < a.nlist) {
+            a.cnt[l] = p0;
+#pragma unroll 1
+            for (int b = 0; b < s; ++b) {
+                long long* u = a.units + 3 * ((long long)u0 + b);
+                u[0] = l;
+                u[1] = p0 + b * a.qb;
+                u[2] = min(a.qb, c - b * a.qb);
+            }
+        }
+        lds_barrier();   // (wsum is written again in the next round)
+    }
+    if (wave == 0 && lane == 0) a.nunits[0] = carry_u;
+}
+
+__global__ void __launch_bounds__(256) lists_fill(const ListArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.npairs) return;
+    bool bad;
+    const long long l = list_of_pair(a, i, &bad);
+    if (l >= 0) a.pairs[atomicAdd(a.cnt + l, 1)] = (int)i;
+}
+
+template <int SRC, int NW, bool CTX, int QB, bool RG = false, bool RT = false, bool LM = false>
 __global__ void __launch_bounds__(64 * kScanWavesMax)
 adc_scan(const ScanArgs a) {
     static_assert(RG == (QB == 1), "one query per workgroup is the probe search's form");
     static_assert(!RT || RG, "a table per range is a form of the probe search");
+    static_assert(!LM || !RG, "the list-major form scores a batch of pairs");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int lane = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
@@ -172,7 +308,34 @@ adc_scan(const ScanArgs a) {
     // the batch's tables, the query innermost: one 16-byte read is four queries' entries
     // (RT: nothing yet, a wave loads the table of a range when it comes to it)
     const long long q0 = (long long)blockIdx.x * QB;
-    for (int e = wave * 64 + lane; !RT && e < mk; e += waves * 64) {
+    // LM: the workgroup's unit, a list and up to QB of the pairs that probe it.  The grid is
+    // the host's bound of the units: a workgroup beyond those there are leaves as a whole,
+    // before any barrier
+    long long u_list = 0, u_first = 0;
+    int u_cnt = 0;
+    if constexpr (LM) {
+        if ((long long)blockIdx.x >= a.nunits[0]) return;
+        u_list = a.units[3 * (long long)blockIdx.x];
+        u_first = a.units[3 * (long long)blockIdx.x + 1];
+        u_cnt = (int)a.units[3 * (long long)blockIdx.x + 2];
+        // slot qq holds the table of its pair (or of the pair's query); a missing slot zeros
+        const float* tab[QB];
+#pragma unroll
+        for (int qq = 0; qq < QB; ++qq) {
+            const long long pair = qq < u_cnt ? a.pairs[u_first + qq] : 0;
+            tab[qq] = a.lut + (a.pair_tables ? pair : pair / a.nprobe) * mk;
+        }
+        for (int e = wave * 64 + lane; e < mk; e += waves * 64) {
+            float v[QB];
+#pragma unroll
+            for (int qq = 0; qq < QB; ++qq) v[qq] = qq < u_cnt ? tab[qq][e] : 0.f;
+#pragma unroll
+            for (int u = 0; u < QB / 4; ++u)
+                reinterpret_cast<float4*>(lut_lds + (size_t)e * QB)[u] =
+                    make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+        }
+    }
+    for (int e = wave * 64 + lane; !RT && !LM && e < mk; e += waves * 64) {
         float v[QB];
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) v[qq] = q0 + qq < a.nq ? a.lut[(q0 + qq) * mk + e] : 0.f;
@@ -199,6 +362,15 @@ adc_scan(const ScanArgs a) {
         } else if (blockIdx.y == 0 && wave == 0 && lane == 0) {
             atomicOr(a.err, 2ull);
         }
+    }
+
+    // LM: the list's rows [l_first, l_first + l_count) -- a good pair with rows, or lists_plan
+    // had made no unit of it -- and the steps of its chunks
+    long long l_first = 0, l_count = 0;
+    if constexpr (LM) {
+        l_first = a.offsets[u_list];
+        l_count = a.offsets[u_list + 1] - l_first;
+        steps = ((l_first + l_count - 1) / C - l_first / C + a.L) / a.L;
     }
 
     TopK list[QB];
@@ -259,9 +431,15 @@ adc_scan(const ScanArgs a) {
                 }
             }
         }
+        if constexpr (LM) {   // the step's chunks of the list, and its rows inside the list
+            j0 = l_first / C + g * a.L;
+            jn = min((l_first + l_count - 1) / C + 1 - j0, (long long)a.L);
+            lo = max(l_first, j0 * C);
+            hi = min(l_first + l_count, (j0 + jn) * C);
+        }
         const long long row0 = j0 * C;
-        const int nrows = (int)(min(a.n, (j0 + (RG ? jn : (long long)a.L)) * C) - row0);
-        const int span = RG ? (int)jn : 64;   // the chunks the stream window is staged for
+        const int nrows = (int)(min(a.n, (j0 + (RG || LM ? jn : (long long)a.L)) * C) - row0);
+        const int span = RG || LM ? (int)jn : 64;   // the chunks the stream window is staged for
         unsigned long long dead = 0;   // lanes whose chunk failed
         if constexpr (SRC == 0) {
             bool use_win = false;
@@ -283,7 +461,7 @@ adc_scan(const ScanArgs a) {
                 const long long j = j0 + lane;
                 const unsigned long long off = a.chunk_off[j];
                 // (RG: a chunk cut by the range's end is decoded up to that end only)
-                const int cnt = (int)min((long long)C, (RG ? hi : a.n) - j * C);
+                const int cnt = (int)min((long long)C, (RG || LM ? hi : a.n) - j * C);
                 const bool raw = CTX && j == 0 && a.raw_first;
                 auto walk = [&](auto& br) -> bool {
                     if constexpr (NW > 0) {
@@ -358,7 +536,7 @@ adc_scan(const ScanArgs a) {
             const int r = base + lane;
             bool valid = r < nrows;
             if (dead && valid) valid = !((dead >> (r / C)) & 1ull);
-            if constexpr (RG) valid = valid && row0 + r >= lo && row0 + r < hi;
+            if constexpr (RG || LM) valid = valid && row0 + r >= lo && row0 + r < hi;
             const unsigned char* row = stage + (long long)(r < nrows ? r : 0) * m;
             float sum[QB];
             auto add = [&](int i, unsigned c) {
@@ -400,7 +578,8 @@ adc_scan(const ScanArgs a) {
             const long long id = row0 + r;
 #pragma unroll
             for (int qq = 0; qq < QB; ++qq)
-                if (q0 + qq < a.nq) list_offer<false>(list[qq], sum[qq], id, valid, kth);
+                if (LM ? qq < u_cnt : q0 + qq < a.nq)
+                    list_offer<false>(list[qq], sum[qq], id, valid, kth);
         }
         wave_lds_sync();   // the next step's staging overwrites what was just read
     }
@@ -417,7 +596,7 @@ adc_scan(const ScanArgs a) {
     }
     lds_barrier();
 #pragma unroll 1
-    for (int qq = wave; qq < QB && q0 + qq < a.nq; qq += waves) {
+    for (int qq = wave; qq < QB && (LM ? qq < u_cnt : q0 + qq < a.nq); qq += waves) {
         TopK e{INFINITY, -1ll};
 #pragma unroll 1
         for (int s = 0; s < waves; ++s) {
@@ -426,7 +605,9 @@ adc_scan(const ScanArgs a) {
             list_offer<true>(e, d, id, id >= 0, kth);
         }
         if (lane < a.top_k) {
-            const long long o = ((q0 + qq) * gridDim.y + blockIdx.y) * a.top_k + lane;
+            // (LM: the pair's lists, one per group -- a group without steps leaves the padding)
+            const long long slot = LM ? (long long)a.pairs[u_first + qq] : q0 + qq;
+            const long long o = (slot * gridDim.y + blockIdx.y) * a.top_k + lane;
             a.part_d[o] = e.d;
             a.part_id[o] = e.id;
         }
@@ -508,8 +689,21 @@ int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long lon
 // row's u64 words (0: per part).  rg: the probe search (a.range_ptr, a.ranges and a.nr set):
 // the plan first, then one query per workgroup.  rt (with rg): a.lut holds one table per
 // range; the stage, the window and so the plan are those of rg, only the waves may be fewer.
+// ls: the list-major probe search (a.offsets, a.nprobe and a.pair_tables set too): the lists_*
+// kernels first, then one workgroup row per unit of the host's bound, and nprobe * groups lists
+// per query for the merge.
+struct ListProbe {
+    const long long* offsets;
+    long long nlist;
+    const long long* probes;
+    int nprobe;
+    bool tables;   // d_lut is [nq * nprobe][m][K]
+};
+constexpr int kListWaves = 16;   // the list-major form: waves per workgroup at the most
+
 int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long id_base,
-                float* d_dist, long long* d_ids, bool rg = false, bool rt = false) {
+                float* d_dist, long long* d_ids, bool rg = false, bool rt = false,
+                const ListProbe* ls = nullptr) {
     if (a.nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
     const int m = a.m, k = a.k;
     // the batch's tables: at most 64 KB; 16-part rows keep to four queries (eight running
@@ -542,7 +736,10 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
     int fit = floor_pow2(std::min<long long>(
         kScanWavesMax, rt ? kLdsBytes / (per_wave + wave_table) : budget / per_wave));
     a.steps = (chunks + a.L - 1) / a.L;
-    const long long batches = (a.nq + qb - 1) / qb;
+    // ls: the units are device data, at most one per pair and at most one part-filled per list
+    const long long npairs = ls ? a.nq * ls->nprobe : 0;
+    const long long batches =
+        ls ? std::min<long long>(npairs, ls->nlist + npairs / qb) : (a.nq + qb - 1) / qb;
     // one workgroup per compute unit over all query batches (a workgroup's tables take most
     // of a compute unit's LDS), each wave with at least two steps where there are that many
     long long groups = ctx->tune_search_groups > 0 ? ctx->tune_search_groups
@@ -563,14 +760,31 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         if (ctx->tune_search_groups <= 0)
             groups = std::min<long long>(wgs, (a.steps + fit - 1) / fit);
         groups = std::min<long long>(std::max<long long>(groups, 1), 65535);
+    } else if (ls) {
+        // the default fills the compute units with the bound's units (a workgroup's tables
+        // take most of a compute unit's LDS) and no list has more steps than the stream; a
+        // group without steps writes the padding
+        if (ctx->tune_search_groups <= 0) groups = std::min<long long>(groups, a.steps);
+        groups = std::min<long long>(groups, 65535);
     } else {
         groups = std::min<long long>(std::min<long long>(groups, a.steps), 65535);
     }
+    // ls: a list's steps are known on the device only; twice the mean list's share of steps
+    // per group, kListWaves at the most
+    const long long mean2 = ls ? 2 * ((a.steps + ls->nlist - 1) / ls->nlist) : 0;
     const int waves =
-        rg ? fit : std::min(fit, floor_pow2((a.steps + 2 * groups - 1) / (2 * groups)));
-    const long long lists = groups;   // (a workgroup merges its waves' lists)
+        rg   ? fit
+        : ls ? std::min(std::min(fit, kListWaves), floor_pow2((mean2 + groups - 1) / groups))
+             : std::min(fit, floor_pow2((a.steps + 2 * groups - 1) / (2 * groups)));
+    // (a workgroup merges its waves' lists; ls: a list per pair and group)
+    const long long lists = ls ? ls->nprobe * groups : groups;
     const size_t entries = (size_t)a.nq * lists * a.top_k;
-    const size_t plan_bytes = rg ? ((size_t)a.nr + 1) * 8 : 0;   // beside the partial lists
+    // beside the partial lists -- rg: the plan; ls: the units [batches][3] and their count,
+    // the lists' counts and the pairs
+    const size_t cnt_bytes = ls ? (((size_t)ls->nlist * 4 + 7) & ~(size_t)7) : 0;
+    const size_t plan_bytes = rg   ? ((size_t)a.nr + 1) * 8
+                              : ls ? ((size_t)batches * 3 + 1) * 8 + cnt_bytes + (size_t)npairs * 4
+                                   : 0;
     int rc = pqh_ensure_ws(ctx, entries * 12 + 16 + plan_bytes);
     if (rc) return rc;
     a.part_id = static_cast<long long*>(ctx->ws);
@@ -583,14 +797,42 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         PQH_LAUNCH_CHECK(ctx);
         a.plan = plan;
     }
+    if (ls) {
+        long long* units = static_cast<long long*>(ctx->ws) + ((entries * 12 + 15) / 8);
+        ListArgs la{};
+        la.offsets = ls->offsets;
+        la.nlist = ls->nlist;
+        la.probes = ls->probes;
+        la.npairs = npairs;
+        la.n = a.n;
+        la.qb = qb;
+        la.pad = groups * a.top_k;
+        la.units = units;
+        la.nunits = units + batches * 3;
+        la.cnt = reinterpret_cast<int*>(la.nunits + 1);
+        la.pairs = reinterpret_cast<int*>(reinterpret_cast<char*>(la.cnt) + cnt_bytes);
+        la.part_d = a.part_d;
+        la.part_id = a.part_id;
+        la.err = a.err;
+        const dim3 by_list((unsigned)((ls->nlist + 255) / 256)), by_pair((unsigned)((npairs + 255) / 256));
+        hipLaunchKernelGGL(lists_zero, by_list, dim3(256), 0, ctx->stream, la);
+        hipLaunchKernelGGL(lists_count, by_pair, dim3(256), 0, ctx->stream, la);
+        hipLaunchKernelGGL(lists_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, la);
+        hipLaunchKernelGGL(lists_fill, by_pair, dim3(256), 0, ctx->stream, la);
+        PQH_LAUNCH_CHECK(ctx);
+        a.units = la.units;
+        a.nunits = la.nunits;
+        a.pairs = la.pairs;
+    }
     // (the end of the kernel exchanges the waves' lists, 12 bytes an entry, through the same LDS)
     const size_t lds = std::max<size_t>(
         rt ? (size_t)waves * (size_t)(wave_table + per_wave)
            : (size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
         (size_t)waves * qb * 64 * 12);
-    auto launch = [&](auto s, auto w, auto c, auto q, auto tb) -> int {
+    auto launch = [&](auto s, auto w, auto c, auto q, auto tb, auto lm) -> int {
         auto* fn = adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
-                            decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value>;
+                            decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value,
+                            decltype(lm)::value>;
         if (lds > 64 * 1024)
             PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -599,11 +841,17 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         return PQH_OK;
     };
     auto with_qb = [&](auto s, auto w, auto c) -> int {
-        if (rt) return launch(s, w, c, Int<1>(), std::true_type());
-        if (rg) return launch(s, w, c, Int<1>(), std::false_type());
+        const std::false_type no;
+        if (rt) return launch(s, w, c, Int<1>(), std::true_type(), no);
+        if (rg) return launch(s, w, c, Int<1>(), no, no);
+        if (ls) {
+            if constexpr (decltype(w)::value != 2)
+                if (qb == 8) return launch(s, w, c, Int<8>(), no, std::true_type());
+            return launch(s, w, c, Int<4>(), no, std::true_type());
+        }
         if constexpr (decltype(w)::value != 2)
-            if (qb == 8) return launch(s, w, c, Int<8>(), std::false_type());
-        return launch(s, w, c, Int<4>(), std::false_type());
+            if (qb == 8) return launch(s, w, c, Int<8>(), no, no);
+        return launch(s, w, c, Int<4>(), no, no);
     };
     auto with_nw = [&](auto s, auto c) -> int {
         return nw == 1 ? with_qb(s, Int<1>(), c) : nw == 2 ? with_qb(s, Int<2>(), c)
@@ -639,6 +887,15 @@ bool ranges_args_ok(long long nq, const long long* d_range_ptr, const long long*
     return nr >= 0 && !(nq > 0 && (!d_range_ptr || (nr > 0 && !d_ranges)));
 }
 
+// the same for the *_lists calls (the values are device data: lists_count), and what the
+// list-major form does not take: 2^31 pairs or lists
+bool lists_args_ok(long long nq, const ListProbe* ls) {
+    return ls->nlist >= 1 && ls->nprobe >= 1 && !(nq > 0 && (!ls->offsets || !ls->probes));
+}
+bool lists_too_many(long long nq, const ListProbe* ls) {
+    return ls->nlist > 0x7FFFFFFFll || nq > 0x7FFFFFFFll / ls->nprobe;
+}
+
 // the probe list of the *_ranges calls
 struct Probe {
     const long long* range_ptr;
@@ -647,19 +904,21 @@ struct Probe {
     bool tables = false;   // the *_range_tables calls: d_lut is [nr][m][K]
 };
 
-// pqh_search_stream (pr = null), pqh_search_stream_ranges and pqh_search_stream_range_tables
+// pqh_search_stream (pr = null), pqh_search_stream_ranges and pqh_search_stream_range_tables;
+// pqh_search_stream_lists (ls)
 int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
                   unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
                   const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
                   const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
-                  float* d_dist, long long* d_ids) {
+                  float* d_dist, long long* d_ids, const ListProbe* ls = nullptr) {
     if (!ctx) return pqh_no_ctx_status();
     if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
     if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
     if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
-    if (t->k > 256 || t->m > 16) return PQH_ERR_UNSUPPORTED;
+    if (ls && !lists_args_ok(nq, ls)) return PQH_ERR_ARG;
+    if (t->k > 256 || t->m > 16 || (ls && lists_too_many(nq, ls))) return PQH_ERR_UNSUPPORTED;
     bool run = false;
     int rc = search_check(ctx, d_stream != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
     if (rc || !run) return rc;
@@ -681,20 +940,23 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
     a.nq = nq;
     a.top_k = top_k;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
+    if (ls) a.offsets = ls->offsets, a.nprobe = ls->nprobe, a.pair_tables = ls->tables;
     // rows of whole u64 words with the chunk contexts readable as such: the packed walk
     const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
     return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, id_base, d_dist, d_ids,
-                       pr != nullptr, pr && pr->tables);
+                       pr != nullptr, pr && pr->tables, ls);
 }
 
-// pqh_search_codes (pr = null), pqh_search_codes_ranges and pqh_search_codes_range_tables
+// pqh_search_codes (pr = null), pqh_search_codes_ranges and pqh_search_codes_range_tables;
+// pqh_search_codes_lists (ls)
 int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                  const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
-                 float* d_dist, long long* d_ids) {
+                 float* d_dist, long long* d_ids, const ListProbe* ls = nullptr) {
     if (!ctx) return pqh_no_ctx_status();
     if (m < 1 || k < 1) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
-    if (k > 256 || m > 16) return PQH_ERR_UNSUPPORTED;
+    if (ls && !lists_args_ok(nq, ls)) return PQH_ERR_ARG;
+    if (k > 256 || m > 16 || (ls && lists_too_many(nq, ls))) return PQH_ERR_UNSUPPORTED;
     bool run = false;
     int rc = search_check(ctx, d_codes != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
     if (rc || !run) return rc;
@@ -710,8 +972,9 @@ int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
     a.nq = nq;
     a.top_k = top_k;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
+    if (ls) a.offsets = ls->offsets, a.nprobe = ls->nprobe, a.pair_tables = ls->tables;
     return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids,
-                       pr != nullptr, pr && pr->tables);
+                       pr != nullptr, pr && pr->tables, ls);
 }
 
 }  // namespace
@@ -794,6 +1057,28 @@ int pqh_search_codes_range_tables(pqh_ctx_t* ctx, const void* d_codes, long long
                                   long long id_base, float* d_dist, long long* d_ids) {
     const Probe pr{d_range_ptr, d_ranges, nr, true};
     return search_codes(ctx, d_codes, n, m, k, d_lut, nq, &pr, top_k, id_base, d_dist, d_ids);
+}
+
+int pqh_search_stream_lists(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                            unsigned long long stream_bytes, long long n, int raw_first,
+                            int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                            const void* d_chunk_prev, const long long* d_offsets, long long nlist,
+                            const long long* d_probes, long long nq, int nprobe,
+                            const float* d_lut, int tables_per_probe, int top_k,
+                            long long id_base, float* d_dist, long long* d_ids) {
+    const ListProbe ls{d_offsets, nlist, d_probes, nprobe, tables_per_probe != 0};
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, nullptr, top_k, id_base, d_dist,
+                         d_ids, &ls);
+}
+
+int pqh_search_codes_lists(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                           const long long* d_offsets, long long nlist, const long long* d_probes,
+                           long long nq, int nprobe, const float* d_lut, int tables_per_probe,
+                           int top_k, long long id_base, float* d_dist, long long* d_ids) {
+    const ListProbe ls{d_offsets, nlist, d_probes, nprobe, tables_per_probe != 0};
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, nullptr, top_k, id_base, d_dist, d_ids,
+                        &ls);
 }
 
 }  // extern "C"
