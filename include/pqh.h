@@ -482,6 +482,81 @@ int pqh_search_codes_lists(pqh_ctx_t* ctx, const void* d_codes, long long n, int
                            long long nq, int nprobe, const float* d_lut, int tables_per_probe,
                            int top_k, long long id_base, float* d_dist, long long* d_ids);
 
+/* Filtered search: every search call above has a _masked counterpart that takes a row mask,
+ * d_keep, after d_ids and returns the call's result restricted to the rows the mask keeps.
+ * The mask is a device array of ceil(n / 32) 32-bit words, one per call and shared by all its
+ * queries: bit r & 31 of word r >> 5 is set when stream row r may be returned.  The bits from
+ * n on in the last word may hold anything and are ignored; the words need 4-byte alignment
+ * only (PQH_ERR_ARG otherwise) and are only read.  pqh_mask_pack makes one from a byte per row.
+ * The result is the unfiltered call's definition over the kept rows: the top_k by (dist, id)
+ * among the rows that are kept and -- in the probe forms -- inside the query's ranges or lists,
+ * dist the same fp32 sum, padded with (+inf, -1), ids moved by id_base, independent of the
+ * grid.  It is not the unfiltered result with the dropped rows taken out: a query gets top_k
+ * kept rows whenever that many are in its reach.
+ * d_keep == NULL is no filter: the call is then the unfiltered one, launch for launch.  The
+ * argument checks, the limits, the scratch and the behaviour of nq == 0, n == 0 and nr == 0 are
+ * the unfiltered call's.
+ * What is not kept is not decoded: a chunk is walked only as far as its last kept row (inside
+ * the range or list, in the probe forms), a chunk without a kept row is neither read nor
+ * walked, and a step of 64 chunks without a kept row costs the read of its mask words.  So the
+ * decode errors (PQH_ERR_CORRUPT from pqh_decode_status) are raised only for the chunks that
+ * are walked, and within them only up to the last kept row, as the range forms raise them only
+ * for the chunks under a range: a damaged chunk whose rows are all masked out is not reported,
+ * and an all-zero mask reports nothing.  The bad ranges, range_ptr entries, probes and offsets
+ * of the probe forms are reported whatever the mask holds. */
+int pqh_search_stream_masked(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                             unsigned long long stream_bytes, long long n, int raw_first,
+                             int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                             const void* d_chunk_prev, const float* d_lut, long long nq, int top_k,
+                             long long id_base, float* d_dist, long long* d_ids,
+                             const unsigned int* d_keep /* [ceil(n / 32)] or NULL */);
+int pqh_search_codes_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                            const float* d_lut, long long nq, int top_k, long long id_base,
+                            float* d_dist, long long* d_ids, const unsigned int* d_keep);
+int pqh_search_stream_ranges_masked(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                    const unsigned char* d_stream, unsigned long long stream_bytes,
+                                    long long n, int raw_first, int chunk_vectors,
+                                    const unsigned long long* d_chunk_offsets,
+                                    const void* d_chunk_prev, const float* d_lut, long long nq,
+                                    const long long* d_range_ptr, const long long* d_ranges,
+                                    long long nr, int top_k, long long id_base, float* d_dist,
+                                    long long* d_ids, const unsigned int* d_keep);
+int pqh_search_codes_ranges_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                                   const float* d_lut, long long nq, const long long* d_range_ptr,
+                                   const long long* d_ranges, long long nr, int top_k,
+                                   long long id_base, float* d_dist, long long* d_ids,
+                                   const unsigned int* d_keep);
+int pqh_search_stream_range_tables_masked(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                          const unsigned char* d_stream,
+                                          unsigned long long stream_bytes, long long n,
+                                          int raw_first, int chunk_vectors,
+                                          const unsigned long long* d_chunk_offsets,
+                                          const void* d_chunk_prev, const float* d_lut,
+                                          long long nq, const long long* d_range_ptr,
+                                          const long long* d_ranges, long long nr, int top_k,
+                                          long long id_base, float* d_dist, long long* d_ids,
+                                          const unsigned int* d_keep);
+int pqh_search_codes_range_tables_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m,
+                                         int k, const float* d_lut, long long nq,
+                                         const long long* d_range_ptr, const long long* d_ranges,
+                                         long long nr, int top_k, long long id_base, float* d_dist,
+                                         long long* d_ids, const unsigned int* d_keep);
+int pqh_search_stream_lists_masked(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                   const unsigned char* d_stream, unsigned long long stream_bytes,
+                                   long long n, int raw_first, int chunk_vectors,
+                                   const unsigned long long* d_chunk_offsets,
+                                   const void* d_chunk_prev, const long long* d_offsets,
+                                   long long nlist, const long long* d_probes, long long nq,
+                                   int nprobe, const float* d_lut, int tables_per_probe, int top_k,
+                                   long long id_base, float* d_dist, long long* d_ids,
+                                   const unsigned int* d_keep);
+int pqh_search_codes_lists_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                                  const long long* d_offsets, long long nlist,
+                                  const long long* d_probes, long long nq, int nprobe,
+                                  const float* d_lut, int tables_per_probe, int top_k,
+                                  long long id_base, float* d_dist, long long* d_ids,
+                                  const unsigned int* d_keep);
+
 /* ---- inverted file: coarse quantizer, list layout, probe selection ---------------------
  * The front end of the probe search: rows are assigned to the nearest of nlist coarse
  * centroids (full d-dimensional vectors), stored list by list, and a query probes the nprobe
@@ -573,8 +648,18 @@ int pqh_adc_tables_residual(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse
                             const long long* d_probes /* [nq][nprobe] */, int nprobe,
                             float* d_lut /* [nq * nprobe][m][K] */);
 
+/* The row mask of the *_masked searches from a byte per row: bit i of d_bits (bit i & 31 of
+ * word i >> 5) = d_keep[p] != 0 with p = d_perm ? d_perm[i] : i -- with pqh_ivf_layout's
+ * d_perm, a predicate over the caller's rows becomes the mask over the stream's.  d_keep u8
+ * [n], d_perm int64 [n] or NULL, d_bits [ceil(n / 32)] words (4-byte aligned, else
+ * PQH_ERR_ARG), all of them written, the bits from n on in the last one as zeros.  A d_perm
+ * entry outside [0, n) reads nothing, gives a zero bit and PQH_ERR_ARG from pqh_ivf_status.
+ * n == 0 launches nothing. */
+int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n], nonzero = keep */,
+                  const long long* d_perm /* [n] or NULL */, long long n, unsigned int* d_bits);
+
 /* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe / pqh_ivf_residuals /
- * pqh_adc_tables_residual on this context since the last call met a bad value (sticky until
+ * pqh_mask_pack / pqh_adc_tables_residual on this context since the last call met a bad value (sticky until
  * read, like pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
 

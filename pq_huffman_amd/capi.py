@@ -171,6 +171,21 @@ SIGNATURES = [
     ("pqh_search_stream_lists", I,
      [P, P, P, ULL, LL, I, I, P, P, P, LL, P, LL, I, P, I, I, LL, P, P]),
     ("pqh_search_codes_lists", I, [P, P, LL, I, I, P, LL, P, LL, I, P, I, I, LL, P, P]),
+    # the *_masked searches: the call's arguments and the mask words behind them
+    ("pqh_search_stream_masked", I, [P, P, P, ULL, LL, I, I, P, P, P, LL, I, LL, P, P, P]),
+    ("pqh_search_codes_masked", I, [P, P, LL, I, I, P, LL, I, LL, P, P, P]),
+    ("pqh_search_stream_ranges_masked", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, LL, P, P, P]),
+    ("pqh_search_codes_ranges_masked", I, [P, P, LL, I, I, P, LL, P, P, LL, I, LL, P, P, P]),
+    ("pqh_search_stream_range_tables_masked", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, LL, P, P, P]),
+    ("pqh_search_codes_range_tables_masked", I,
+     [P, P, LL, I, I, P, LL, P, P, LL, I, LL, P, P, P]),
+    ("pqh_search_stream_lists_masked", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, LL, I, P, I, I, LL, P, P, P]),
+    ("pqh_search_codes_lists_masked", I,
+     [P, P, LL, I, I, P, LL, P, LL, I, P, I, I, LL, P, P, P]),
+    ("pqh_mask_pack", I, [P, P, P, LL, P]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

@@ -20,6 +20,8 @@ calls on device-resident data:
                          IVF.build(residual=True))
     search_lists         the probe search in list-major order: a list decoded once per batch of
                          the queries that probe it (IVF.search(schedule="list"))
+    pack_mask, keep=     filtered search: a bit per stream row, rows and chunks that are not kept
+                         are not decoded (IVF.search(keep=...), IVF.remove)
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
@@ -636,29 +638,66 @@ def _search_out(lut, k, out):
             torch.empty((nq, k), dtype=torch.int64, device=lut.device))
 
 
-def search(ctx: Context, tables: Tables, enc: Encoded, lut, k: int, id_base: int = 0, out=None):
+def pack_mask(ctx: Context, keep, perm=None, out=None):
+    """the row mask of the searches' keep= from a flag per row: int32 (ceil(n / 32),), bit
+    i & 31 of word i >> 5 = keep[perm[i]] (perm None: keep[i]) (pqh_mask_pack).  keep: device
+    bool or uint8 (n,), nonzero = the row may be returned; perm: device int64 (n,), e.g. an
+    IVF's (stream row -> caller row).  Async; ivf_status reports a perm entry outside [0, n)
+    (its bit is zero)."""
+    torch = _torch()
+    n = keep.numel()
+    if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1:
+        raise PqhError(-1, "pack_mask: keep is a bool or uint8 tensor of shape (n,)")
+    if perm is not None and perm.numel() != n:
+        raise PqhError(-1, f"pack_mask: {perm.numel()} perm entries for {n} rows")
+    keep = keep.contiguous()
+    if perm is not None and not perm.is_contiguous():
+        perm = perm.contiguous()
+    if out is None:
+        out = torch.empty((n + 31) // 32, dtype=torch.int32, device=keep.device)
+    check(lib().pqh_mask_pack(ctx.ptr, _ptr(keep), _ptr(perm), n, _ptr(out)), "pqh_mask_pack")
+    return out
+
+
+def _entry(name: str, keep, n: int):
+    """(entry point, its trailing arguments): today's call without a mask, the _masked one
+    with the words behind d_ids.  keep: device int32, at least ceil(n / 32) words."""
+    if keep is None:
+        return getattr(lib(), name), ()
+    if keep.dtype != _torch().int32 or not keep.is_contiguous() or keep.numel() < (n + 31) // 32:
+        raise PqhError(-1, f"{name}: keep is a contiguous int32 tensor of ceil(n / 32) words")
+    return getattr(lib(), name + "_masked"), (_ptr(keep),)
+
+
+def search(ctx: Context, tables: Tables, enc: Encoded, lut, k: int, id_base: int = 0, out=None,
+           keep=None):
     """(dist, ids), each (nq, k): per query table lut[q] (float32 (m, K)) the k rows of the
     stream with the smallest summed entries, ascending by (dist, id), ids = stream rows +
     id_base, padded with (+inf, -1); the stream is decoded and scored in one kernel, the
     codes never written (pqh_search_stream).  Async; decode_status reports a corrupt stream.
-    out: a (dist, ids) pair to fill."""
+    out: a (dist, ids) pair to fill.
+    keep: the row mask, device int32 words as pack_mask makes them (bit r & 31 of word r >> 5 =
+    stream row r may be returned; the bits from n on are ignored).  The result is then the top k
+    among the kept rows, and what is not kept is not decoded (pqh_search_stream_masked); this
+    holds for every search_* function below."""
     dist, ids = _search_out(lut, k, out)
-    check(lib().pqh_search_stream(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut), lut.shape[0],
-                                  k, id_base, _ptr(dist), _ptr(ids)), "pqh_search_stream")
+    fn, mask = _entry("pqh_search_stream", keep, enc.n)
+    check(fn(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut), lut.shape[0], k, id_base,
+             _ptr(dist), _ptr(ids), *mask), "pqh_search_stream")
     return dist, ids
 
 
-def search_codes(ctx: Context, codes, lut, k: int, id_base: int = 0, out=None):
+def search_codes(ctx: Context, codes, lut, k: int, id_base: int = 0, out=None, keep=None):
     """search() over plain uint8 codes (n, m) (pqh_search_codes)."""
     dist, ids = _search_out(lut, k, out)
-    check(lib().pqh_search_codes(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1],
-                                 lut.shape[2], _ptr(lut), lut.shape[0], k, id_base, _ptr(dist),
-                                 _ptr(ids)), "pqh_search_codes")
+    fn, mask = _entry("pqh_search_codes", keep, codes.shape[0])
+    check(fn(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1], lut.shape[2], _ptr(lut),
+             lut.shape[0], k, id_base, _ptr(dist), _ptr(ids), *mask), "pqh_search_codes")
     return dist, ids
 
 
 def search_ranges(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ranges, k: int,
-                  id_base: int = 0, out=None):
+                  id_base: int = 0, out=None, keep=None):
     """search() of per-query row ranges, the way an inverted file is probed: query q scores
     only the rows [ranges[r, 0], ranges[r, 0] + ranges[r, 1]) for r in
     [range_ptr[q], range_ptr[q + 1]), and only the chunks under them are decoded
@@ -667,21 +706,21 @@ def search_ranges(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ra
     Async; decode_status reports a corrupt chunk that was walked (PQH_ERR_CORRUPT) or a bad
     range or range_ptr value (PQH_ERR_ARG, the range or query skipped)."""
     dist, ids = _search_out(lut, k, out)
-    check(lib().pqh_search_stream_ranges(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut),
-                                         lut.shape[0], _ptr(range_ptr), _ptr(ranges),
-                                         ranges.shape[0], k, id_base, _ptr(dist), _ptr(ids)),
+    fn, mask = _entry("pqh_search_stream_ranges", keep, enc.n)
+    check(fn(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut), lut.shape[0], _ptr(range_ptr),
+             _ptr(ranges), ranges.shape[0], k, id_base, _ptr(dist), _ptr(ids), *mask),
           "pqh_search_stream_ranges")
     return dist, ids
 
 
 def search_codes_ranges(ctx: Context, codes, lut, range_ptr, ranges, k: int, id_base: int = 0,
-                        out=None):
+                        out=None, keep=None):
     """search_ranges() over plain uint8 codes (n, m) (pqh_search_codes_ranges)."""
     dist, ids = _search_out(lut, k, out)
-    check(lib().pqh_search_codes_ranges(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1],
-                                        lut.shape[2], _ptr(lut), lut.shape[0], _ptr(range_ptr),
-                                        _ptr(ranges), ranges.shape[0], k, id_base, _ptr(dist),
-                                        _ptr(ids)), "pqh_search_codes_ranges")
+    fn, mask = _entry("pqh_search_codes_ranges", keep, codes.shape[0])
+    check(fn(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1], lut.shape[2], _ptr(lut),
+             lut.shape[0], _ptr(range_ptr), _ptr(ranges), ranges.shape[0], k, id_base, _ptr(dist),
+             _ptr(ids), *mask), "pqh_search_codes_ranges")
     return dist, ids
 
 
@@ -713,29 +752,26 @@ def _range_search_out(range_ptr, k, out):
 
 
 def search_range_tables(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ranges,
-                        k: int, id_base: int = 0, out=None):
+                        k: int, id_base: int = 0, out=None, keep=None):
     """search_ranges() with one table per range: lut float32 (nr, m, K), range r scored with
     lut[r] (pqh_search_stream_range_tables) -- the probe search of a residual inverted file,
     lut from adc_tables_residual.  The number of queries is range_ptr.numel() - 1."""
     dist, ids = _range_search_out(range_ptr, k, out)
-    check(lib().pqh_search_stream_range_tables(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut),
-                                               range_ptr.numel() - 1, _ptr(range_ptr),
-                                               _ptr(ranges), ranges.shape[0], k, id_base,
-                                               _ptr(dist), _ptr(ids)),
-          "pqh_search_stream_range_tables")
+    fn, mask = _entry("pqh_search_stream_range_tables", keep, enc.n)
+    check(fn(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(lut), range_ptr.numel() - 1,
+             _ptr(range_ptr), _ptr(ranges), ranges.shape[0], k, id_base, _ptr(dist), _ptr(ids),
+             *mask), "pqh_search_stream_range_tables")
     return dist, ids
 
 
 def search_codes_range_tables(ctx: Context, codes, lut, range_ptr, ranges, k: int,
-                              id_base: int = 0, out=None):
+                              id_base: int = 0, out=None, keep=None):
     """search_range_tables() over plain uint8 codes (n, m) (pqh_search_codes_range_tables)."""
     dist, ids = _range_search_out(range_ptr, k, out)
-    check(lib().pqh_search_codes_range_tables(ctx.ptr, _ptr(codes), codes.shape[0],
-                                              codes.shape[1], lut.shape[2], _ptr(lut),
-                                              range_ptr.numel() - 1, _ptr(range_ptr),
-                                              _ptr(ranges), ranges.shape[0], k, id_base,
-                                              _ptr(dist), _ptr(ids)),
-          "pqh_search_codes_range_tables")
+    fn, mask = _entry("pqh_search_codes_range_tables", keep, codes.shape[0])
+    check(fn(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1], lut.shape[2], _ptr(lut),
+             range_ptr.numel() - 1, _ptr(range_ptr), _ptr(ranges), ranges.shape[0], k, id_base,
+             _ptr(dist), _ptr(ids), *mask), "pqh_search_codes_range_tables")
     return dist, ids
 
 
@@ -759,7 +795,7 @@ def _lists_args(lut, offsets, probes, k, out):
 
 
 def search_lists(ctx: Context, tables: Tables, enc: Encoded, lut, offsets, probes, k: int,
-                 id_base: int = 0, out=None):
+                 id_base: int = 0, out=None, keep=None):
     """the probe search in list-major order (pqh_search_stream_lists): the result of
     search_ranges (lut float32 (nq, m, K)) or search_range_tables (lut (nq * nprobe, m, K)) on
     probe_ranges(offsets, probes), bit for bit, but a list probed by several queries is decoded
@@ -769,21 +805,21 @@ def search_lists(ctx: Context, tables: Tables, enc: Encoded, lut, offsets, probe
     (PQH_ERR_CORRUPT) or a probe outside [-1, nlist) or a bad offsets pair of a probed list
     (PQH_ERR_ARG, the probe skipped)."""
     nlist, probes, nq, nprobe, per_probe, dist, ids = _lists_args(lut, offsets, probes, k, out)
-    check(lib().pqh_search_stream_lists(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(offsets),
-                                        nlist, _ptr(probes), nq, nprobe, _ptr(lut), per_probe, k,
-                                        id_base, _ptr(dist), _ptr(ids)),
+    fn, mask = _entry("pqh_search_stream_lists", keep, enc.n)
+    check(fn(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(offsets), nlist, _ptr(probes), nq,
+             nprobe, _ptr(lut), per_probe, k, id_base, _ptr(dist), _ptr(ids), *mask),
           "pqh_search_stream_lists")
     return dist, ids
 
 
 def search_codes_lists(ctx: Context, codes, lut, offsets, probes, k: int, id_base: int = 0,
-                       out=None):
+                       out=None, keep=None):
     """search_lists() over plain uint8 codes (n, m) (pqh_search_codes_lists)."""
     nlist, probes, nq, nprobe, per_probe, dist, ids = _lists_args(lut, offsets, probes, k, out)
-    check(lib().pqh_search_codes_lists(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1],
-                                       lut.shape[2], _ptr(offsets), nlist, _ptr(probes), nq,
-                                       nprobe, _ptr(lut), per_probe, k, id_base, _ptr(dist),
-                                       _ptr(ids)), "pqh_search_codes_lists")
+    fn, mask = _entry("pqh_search_codes_lists", keep, codes.shape[0])
+    check(fn(ctx.ptr, _ptr(codes), codes.shape[0], codes.shape[1], lut.shape[2], _ptr(offsets),
+             nlist, _ptr(probes), nq, nprobe, _ptr(lut), per_probe, k, id_base, _ptr(dist),
+             _ptr(ids), *mask), "pqh_search_codes_lists")
     return dist, ids
 
 
@@ -913,8 +949,9 @@ class Coarse:
 
 def ivf_status(ctx: Context) -> None:
     """raises PQH_ERR_ARG if a Coarse.layout / Coarse.probe / Coarse.residuals /
-    adc_tables_residual since the last call met a bad value (a list id outside [0, nlist), a
-    reversed offsets pair, a perm entry outside [0, n)); synchronises (pqh_ivf_status)"""
+    adc_tables_residual / pack_mask since the last call met a bad value (a list id outside
+    [0, nlist), a reversed offsets pair, a perm entry outside [0, n)); synchronises
+    (pqh_ivf_status)"""
     st = lib().pqh_ivf_status(ctx.ptr)
     if st:
         raise PqhError(st, "pqh_ivf")
@@ -936,6 +973,11 @@ class IVF:
     nq * nprobe * m * K * 4 bytes, so search() walks the queries in slabs whose tables stay
     under `table_budget` bytes.
 
+    search(keep=...) searches a subset of the rows, and remove(ids) takes rows out of every
+    later search (tombstones: the stream keeps them, the searches pass over them).  Both are a
+    bit per stream row that the scan reads before it decodes: a chunk without a kept row is not
+    decoded, a list without one costs the read of its mask words.
+
     Every stage is a call on the context's stream.  search() never waits for the device;
     build() waits where encode() does, once, for the stream's length."""
 
@@ -951,6 +993,8 @@ class IVF:
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
         self.perm, self.inv, self.offsets = perm, inv, offsets
         self.residual = residual
+        self.live = None         # remove(): device bool per stream row, allocated on first use
+        self._live_words = None  # its packed form, made again after a remove()
 
     @classmethod
     def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
@@ -975,33 +1019,66 @@ class IVF:
         inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
         return cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
 
-    def search(self, queries, nprobe: int, k: int, schedule: str = "query"):
+    def remove(self, ids) -> None:
+        """take the caller rows `ids` (device int64, each in [0, n)) out of every later search,
+        with or without keep=.  Tombstones: a live flag per stream row is cleared, the stream
+        is not rebuilt, so fetch() still returns a removed row and the index does not shrink.
+        Removing a row twice is harmless.  Async."""
+        torch = _torch()
+        if self.live is None:
+            self.live = torch.ones(self.perm.numel(), dtype=torch.bool, device=self.perm.device)
+        self.live[self.inv[ids.reshape(-1)]] = False
+        self._live_words = pack_mask(self.ctx, self.live)
+
+    def live_count(self) -> int:
+        """the rows remove() has left (synchronises once a row was removed)"""
+        return self.perm.numel() if self.live is None else int(self.live.sum().item())
+
+    def _mask(self, keep):
+        """the words of keep (bool over the caller's rows, packed through perm into stream
+        order) ANDed with those of the live rows; None: no filter"""
+        torch = _torch()
+        if keep is None:
+            return self._live_words
+        if keep.dtype != torch.bool or keep.shape != (self.perm.numel(),):
+            raise PqhError(-1, "IVF.search: keep is a bool tensor of shape (n,)")
+        words = pack_mask(self.ctx, keep, self.perm)
+        return words if self._live_words is None else words & self._live_words
+
+    def search(self, queries, nprobe: int, k: int, schedule: str = "query", keep=None):
         """(dist, ids), each (nq, k): the k nearest rows by ADC distance among the rows of each
         query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1).
         schedule: "query" decodes a list once for every query that probes it (search_ranges),
         "list" once per batch of the queries that probe it (search_lists), "auto" takes "list"
-        from nq * nprobe >= list_major_ratio * nlist on; the result is the same bits."""
+        from nq * nprobe >= list_major_ratio * nlist on; the result is the same bits.
+        keep: device bool (n,) over the caller's rows of x: only rows with keep[id] set are
+        returned -- the k nearest among them, not the kept ones of the k nearest.  Rows taken
+        out by remove() are never returned."""
         torch = _torch()
         if schedule not in ("query", "list", "auto"):
             raise PqhError(-1, f"IVF.search: schedule {schedule!r}")
         by_list = schedule == "list" or (
             schedule == "auto" and
             queries.shape[0] * nprobe >= self.list_major_ratio * self.coarse.nlist)
+        mask = self._mask(keep)
         if self.residual:
-            dist, rows = self._search_residual(queries, nprobe, k, by_list)
+            dist, rows = self._search_residual(queries, nprobe, k, by_list, mask)
             return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
         lut = adc_tables(self.ctx, self.pq, queries)
         range_ptr, ranges, probes, _ = self.coarse.probe(queries, nprobe, self.offsets,
                                                          lists=by_list)
         if by_list:
-            dist, rows = search_lists(self.ctx, self.tables, self.enc, lut, self.offsets, probes, k)
+            dist, rows = search_lists(self.ctx, self.tables, self.enc, lut, self.offsets, probes, k,
+                                      keep=mask)
         else:
-            dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k)
+            dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
+                                       keep=mask)
         return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
 
-    def _search_residual(self, queries, nprobe: int, k: int, by_list: bool = False):
+    def _search_residual(self, queries, nprobe: int, k: int, by_list: bool = False, mask=None):
         """(dist, stream rows): probe, one table per (query, list), the probe search with a
-        table per range (by_list: per pair, list-major) -- slab by slab, the table buffer reused"""
+        table per range (by_list: per pair, list-major) -- slab by slab, the table buffer reused;
+        mask: the words of the rows that may be returned, the same for every slab"""
         torch = _torch()
         nq = queries.shape[0]
         per_query = nprobe * self.pq.m * self.pq.k * 4
@@ -1018,16 +1095,17 @@ class IVF:
             out = (dist[s:s + slab], rows[s:s + slab])
             if by_list:
                 search_lists(self.ctx, self.tables, self.enc, lut[:q.shape[0] * nprobe],
-                             self.offsets, probes, k, out=out)
+                             self.offsets, probes, k, out=out, keep=mask)
             else:
                 search_range_tables(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
-                                    out=out)
+                                    out=out, keep=mask)
         return dist, rows
 
     def fetch(self, ids, out=None):
         """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)), for
         an exact re-rank (fetch through the inverse permutation; residual: the decoded
-        residual plus the centroid of the stream row's list, one fp32 add)"""
+        residual plus the centroid of the stream row's list, one fp32 add).  remove() does not
+        affect it: the stream still holds a removed row."""
         torch = _torch()
         rows = self.inv[ids.reshape(-1)]
         out = fetch(self.ctx, self.tables, self.pq, self.enc, rows, out)

@@ -18,6 +18,8 @@
 //  ivf_layout     rocPRIM's stable radix_sort_pairs of (list id, row number) over
 //                 ceil(log2 nlist) bits, then one kernel: every offset by a binary search in
 //                 the sorted ids, and the check of the ids.
+//  mask_pack      a byte per caller row into the bit per stream row the *_masked searches take,
+//                 through the layout's permutation.
 // The residual form (the stream holds the PQ codes of x - c[list]):
 //  ivf_residual   out[s] = x[perm[s]] - c[list[perm[s]]], the gather into list order and the
 //                 subtract in one pass.  A half wave owns a row and reads 32 consecutive floats
@@ -345,6 +347,26 @@ adc_lut_residual(const float* __restrict__ queries, long long ld_q, int nprobe,
     }
 }
 
+// bit i of the mask = keep[perm ? perm[i] : i] != 0: one lane per row, the wave's 64 bits by a
+// ballot, its two words stored by lanes 0 and 1 (the bits from n on in the last word are zero).
+// A perm entry outside [0, n) reads nothing, gives a zero bit and sets the error word.
+__global__ void __launch_bounds__(256)
+mask_pack(const unsigned char* __restrict__ keep, const long long* __restrict__ perm, long long n,
+          uint32_t* __restrict__ bits, unsigned long long* __restrict__ err) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool bit = false, bad = false;
+    if (i < n) {
+        const long long p = perm ? perm[i] : i;
+        bad = p < 0 || p >= n;
+        if (!bad) bit = keep[p] != 0;
+    }
+    const unsigned long long b = __ballot(bit);
+    const long long w = ((i - lane) >> 5) + lane;   // lanes 0 and 1: the wave's two words
+    if (lane < 2 && w < (n + 31) >> 5) bits[w] = (uint32_t)(b >> (32 * lane));
+    if (__ballot(bad) && lane == 0) atomicOr(err, 1ull);
+}
+
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -509,6 +531,22 @@ int pqh_adc_tables_residual(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse
                        (size_t)cq->d * 4, ctx->stream, d_queries, ld_q, nprobe, d_probes,
                        cq->d_cent, cq->nlist, d_cent, m, k, dsub, vec, d_lut,
                        ctx->d_diag + kDiagIvf);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep, const long long* d_perm, long long n,
+                  unsigned int* d_bits) {
+    if (!ctx) return pqh_no_ctx_status();
+    if (n < 0 || (n > 0 && (!d_keep || !d_bits)) || (reinterpret_cast<uintptr_t>(d_bits) & 3u))
+        return PQH_ERR_ARG;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (n == 0) return PQH_OK;
+    const long long blocks = (n + 255) / 256;
+    if (blocks > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(mask_pack, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_keep, d_perm,
+                       n, d_bits, ctx->d_diag + kDiagIvf);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
 }

@@ -19,6 +19,10 @@
 //              LM = 1 (the list-major probe search, QB = 8 or 4): a workgroup holds a list
 //              and the tables of up to QB of the (query, probe) pairs that probe it, so a step
 //              of the list is decoded once for all of them; its lists go to the pairs' slots.
+//              FL = 1 (the *_masked calls, every form above): a bit per stream row says whether
+//              the row may be returned.  A lane decodes its chunk as far as its last kept row
+//              (not at all without one), and a step without a kept row is passed over before
+//              its window, its rows or (RT) its table are loaded.
 //  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
 //  lists_*     the probe list turned round for LM: the pairs of every list in CSR form
 //              (count, scan, fill), cut into work units of up to QB pairs.
@@ -111,8 +115,26 @@ struct ScanArgs {
             const int* pairs;           // the pairs q * nprobe + p of every list, list by list
         };
     };
+    const uint32_t* keep;       // FL: bit r & 31 of word r >> 5 = row r may be returned (at the
+                                // end: the fields the other forms read stay where they were)
 };
-static_assert(sizeof(ScanArgs) == sizeof(DecTabs) + 168, "LM's fields must not move the others");
+static_assert(sizeof(ScanArgs) == sizeof(DecTabs) + 176, "FL's field must not move the others");
+
+// FL: the rows a lane has to decode of its chunk, of which [r_lo, r_hi) are inside the step's
+// rows: up to the last kept one of them, 0 without one.  Bits outside [r_lo, r_hi) are masked
+// off, so nothing past row n of the last word counts (r_hi <= n) and no word beyond it is read.
+__device__ __forceinline__ int kept_rows(const uint32_t* __restrict__ keep, long long chunk_row0,
+                                         long long r_lo, long long r_hi) {
+    if (r_hi <= r_lo) return 0;
+    const long long w_lo = r_lo >> 5, w_hi = (r_hi - 1) >> 5;
+    for (long long w = w_hi; w >= w_lo; --w) {
+        uint32_t v = keep[w];
+        if (w == w_hi) v &= 0xFFFFFFFFu >> (31 - (int)((r_hi - 1) & 31));
+        if (w == w_lo) v &= 0xFFFFFFFFu << (int)(r_lo & 31);
+        if (v) return (int)(w * 32 + (31 - __clz((int)v)) - chunk_row0) + 1;
+    }
+    return 0;
+}
 
 // The chunks of a good range: [first / C, (first + count - 1) / C + 1); a range is good when
 // 0 <= first <= n and 0 <= count <= n - first (no sum that could overflow).
@@ -283,7 +305,8 @@ __global__ void __launch_bounds__(256) lists_fill(const ListArgs a) {
     if (l >= 0) a.pairs[atomicAdd(a.cnt + l, 1)] = (int)i;
 }
 
-template <int SRC, int NW, bool CTX, int QB, bool RG = false, bool RT = false, bool LM = false>
+template <int SRC, int NW, bool CTX, int QB, bool RG = false, bool RT = false, bool LM = false,
+          bool FL = false>
 __global__ void __launch_bounds__(64 * kScanWavesMax)
 adc_scan(const ScanArgs a) {
     static_assert(RG == (QB == 1), "one query per workgroup is the probe search's form");
@@ -398,6 +421,11 @@ adc_scan(const ScanArgs a) {
         long long j0 = g * a.L;
         long long jn = min(chunks - j0, (long long)a.L);
         long long lo = 0, hi = 0;   // RG: the step's rows inside its range are [lo, hi)
+        // FL: the rows the lane decodes of its chunk.  A step none of whose chunks has a kept
+        // row is left here: nothing of it is staged, and the wave_lds_sync that ended the step
+        // before stands for it too (the loop has no barrier of the workgroup, and the waves'
+        // trip counts differ anyway)
+        int fl_cnt = 0;
         if constexpr (RG) {
             // the step's range: the last one of [r_cur, r_hi) whose steps begin at or before
             // it (ranges without steps share their successor's entry and are passed over)
@@ -415,6 +443,11 @@ adc_scan(const ScanArgs a) {
             jn = min((first + count - 1) / C + 1 - j0, (long long)a.L);
             lo = max(first, j0 * C);
             hi = min(first + count, (j0 + jn) * C);
+            if constexpr (FL) {
+                if (lane < jn) fl_cnt = kept_rows(a.keep, (j0 + lane) * C, max(lo, (j0 + lane) * C),
+                                                  min(hi, (j0 + lane + 1) * C));
+                if (!__ballot(fl_cnt > 0)) continue;   // (before the table: a step without a kept row)
+            }
             if constexpr (RT) {
                 // (the reads of the table before are done: the wave_lds_sync that ends a step;
                 // the new one is complete at the wave_lds_sync before the scoring)
@@ -439,6 +472,12 @@ adc_scan(const ScanArgs a) {
         }
         const long long row0 = j0 * C;
         const int nrows = (int)(min(a.n, (j0 + (RG || LM ? jn : (long long)a.L)) * C) - row0);
+        if constexpr (FL && !RG) {
+            const long long s_lo = LM ? lo : row0, s_hi = LM ? hi : row0 + nrows;
+            if (lane < jn) fl_cnt = kept_rows(a.keep, (j0 + lane) * C, max(s_lo, (j0 + lane) * C),
+                                              min(s_hi, (j0 + lane + 1) * C));
+            if (!__ballot(fl_cnt > 0)) continue;
+        }
         const int span = RG || LM ? (int)jn : 64;   // the chunks the stream window is staged for
         unsigned long long dead = 0;   // lanes whose chunk failed
         if constexpr (SRC == 0) {
@@ -457,11 +496,12 @@ adc_scan(const ScanArgs a) {
             }
             wave_lds_sync();
             bool ok = true;
-            if (lane < jn) {
+            if (lane < jn && (!FL || fl_cnt > 0)) {
                 const long long j = j0 + lane;
                 const unsigned long long off = a.chunk_off[j];
-                // (RG: a chunk cut by the range's end is decoded up to that end only)
-                const int cnt = (int)min((long long)C, (RG || LM ? hi : a.n) - j * C);
+                // (RG: a chunk cut by the range's end is decoded up to that end only; FL: up to
+                // its last kept row, and one without a kept row is not looked at)
+                const int cnt = FL ? fl_cnt : (int)min((long long)C, (RG || LM ? hi : a.n) - j * C);
                 const bool raw = CTX && j == 0 && a.raw_first;
                 auto walk = [&](auto& br) -> bool {
                     if constexpr (NW > 0) {
@@ -537,6 +577,11 @@ adc_scan(const ScanArgs a) {
             bool valid = r < nrows;
             if (dead && valid) valid = !((dead >> (r / C)) & 1ull);
             if constexpr (RG || LM) valid = valid && row0 + r >= lo && row0 + r < hi;
+            if constexpr (FL)   // (the word of a row < n; the stage slots of rows no lane
+                                // decoded hold anything and are not valid)
+                if (r < nrows) valid = valid && ((a.keep[(row0 + r) >> 5] >> ((row0 + r) & 31)) & 1u);
+            if constexpr (FL)   // (64 rows none of which takes part: no sums, nothing to offer)
+                if (!__ballot(valid)) continue;
             const unsigned char* row = stage + (long long)(r < nrows ? r : 0) * m;
             float sum[QB];
             auto add = [&](int i, unsigned c) {
@@ -829,16 +874,21 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         rt ? (size_t)waves * (size_t)(wave_table + per_wave)
            : (size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
         (size_t)waves * qb * 64 * 12);
-    auto launch = [&](auto s, auto w, auto c, auto q, auto tb, auto lm) -> int {
+    auto launch_fl = [&](auto s, auto w, auto c, auto q, auto tb, auto lm, auto fl) -> int {
         auto* fn = adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
                             decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value,
-                            decltype(lm)::value>;
+                            decltype(lm)::value, decltype(fl)::value>;
         if (lds > 64 * 1024)
             PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(fn, dim3((unsigned)batches, (unsigned)groups), dim3(64, waves), lds,
                            ctx->stream, a);
         return PQH_OK;
+    };
+    // a.keep set (the *_masked calls): the filtered form of the same kernel
+    auto launch = [&](auto s, auto w, auto c, auto q, auto tb, auto lm) -> int {
+        return a.keep ? launch_fl(s, w, c, q, tb, lm, std::true_type())
+                      : launch_fl(s, w, c, q, tb, lm, std::false_type());
     };
     auto with_qb = [&](auto s, auto w, auto c) -> int {
         const std::false_type no;
@@ -910,11 +960,13 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
                   unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
                   const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
                   const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
-                  float* d_dist, long long* d_ids, const ListProbe* ls = nullptr) {
+                  float* d_dist, long long* d_ids, const ListProbe* ls = nullptr,
+                  const unsigned int* d_keep = nullptr) {
     if (!ctx) return pqh_no_ctx_status();
     if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
     if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_stream) | reinterpret_cast<uintptr_t>(d_keep)) & 3u)
+        return PQH_ERR_ARG;
     if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
     if (ls && !lists_args_ok(nq, ls)) return PQH_ERR_ARG;
@@ -939,6 +991,7 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
     a.lut = d_lut;
     a.nq = nq;
     a.top_k = top_k;
+    a.keep = d_keep;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
     if (ls) a.offsets = ls->offsets, a.nprobe = ls->nprobe, a.pair_tables = ls->tables;
     // rows of whole u64 words with the chunk contexts readable as such: the packed walk
@@ -951,9 +1004,10 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
 // pqh_search_codes_lists (ls)
 int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                  const float* d_lut, long long nq, const Probe* pr, int top_k, long long id_base,
-                 float* d_dist, long long* d_ids, const ListProbe* ls = nullptr) {
+                 float* d_dist, long long* d_ids, const ListProbe* ls = nullptr,
+                 const unsigned int* d_keep = nullptr) {
     if (!ctx) return pqh_no_ctx_status();
-    if (m < 1 || k < 1) return PQH_ERR_ARG;
+    if (m < 1 || k < 1 || (reinterpret_cast<uintptr_t>(d_keep) & 3u)) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
     if (ls && !lists_args_ok(nq, ls)) return PQH_ERR_ARG;
     if (k > 256 || m > 16 || (ls && lists_too_many(nq, ls))) return PQH_ERR_UNSUPPORTED;
@@ -971,6 +1025,7 @@ int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
     a.lut = d_lut;
     a.nq = nq;
     a.top_k = top_k;
+    a.keep = d_keep;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
     if (ls) a.offsets = ls->offsets, a.nprobe = ls->nprobe, a.pair_tables = ls->tables;
     return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids,
@@ -1079,6 +1134,102 @@ int pqh_search_codes_lists(pqh_ctx_t* ctx, const void* d_codes, long long n, int
     const ListProbe ls{d_offsets, nlist, d_probes, nprobe, tables_per_probe != 0};
     return search_codes(ctx, d_codes, n, m, k, d_lut, nq, nullptr, top_k, id_base, d_dist, d_ids,
                         &ls);
+}
+
+// The *_masked calls: the same entry with d_keep behind d_ids (NULL: the call above, kernel
+// for kernel).
+int pqh_search_stream_masked(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                             unsigned long long stream_bytes, long long n, int raw_first,
+                             int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                             const void* d_chunk_prev, const float* d_lut, long long nq, int top_k,
+                             long long id_base, float* d_dist, long long* d_ids,
+                             const unsigned int* d_keep) {
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, nullptr, top_k, id_base, d_dist,
+                         d_ids, nullptr, d_keep);
+}
+
+int pqh_search_codes_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                            const float* d_lut, long long nq, int top_k, long long id_base,
+                            float* d_dist, long long* d_ids, const unsigned int* d_keep) {
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, nullptr, top_k, id_base, d_dist, d_ids,
+                        nullptr, d_keep);
+}
+
+int pqh_search_stream_ranges_masked(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                    const unsigned char* d_stream, unsigned long long stream_bytes,
+                                    long long n, int raw_first, int chunk_vectors,
+                                    const unsigned long long* d_chunk_offsets,
+                                    const void* d_chunk_prev, const float* d_lut, long long nq,
+                                    const long long* d_range_ptr, const long long* d_ranges,
+                                    long long nr, int top_k, long long id_base, float* d_dist,
+                                    long long* d_ids, const unsigned int* d_keep) {
+    const Probe pr{d_range_ptr, d_ranges, nr};
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, &pr, top_k, id_base, d_dist,
+                         d_ids, nullptr, d_keep);
+}
+
+int pqh_search_codes_ranges_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                                   const float* d_lut, long long nq, const long long* d_range_ptr,
+                                   const long long* d_ranges, long long nr, int top_k,
+                                   long long id_base, float* d_dist, long long* d_ids,
+                                   const unsigned int* d_keep) {
+    const Probe pr{d_range_ptr, d_ranges, nr};
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, &pr, top_k, id_base, d_dist, d_ids,
+                        nullptr, d_keep);
+}
+
+int pqh_search_stream_range_tables_masked(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                          const unsigned char* d_stream,
+                                          unsigned long long stream_bytes, long long n,
+                                          int raw_first, int chunk_vectors,
+                                          const unsigned long long* d_chunk_offsets,
+                                          const void* d_chunk_prev, const float* d_lut,
+                                          long long nq, const long long* d_range_ptr,
+                                          const long long* d_ranges, long long nr, int top_k,
+                                          long long id_base, float* d_dist, long long* d_ids,
+                                          const unsigned int* d_keep) {
+    const Probe pr{d_range_ptr, d_ranges, nr, true};
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, &pr, top_k, id_base, d_dist,
+                         d_ids, nullptr, d_keep);
+}
+
+int pqh_search_codes_range_tables_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m,
+                                         int k, const float* d_lut, long long nq,
+                                         const long long* d_range_ptr, const long long* d_ranges,
+                                         long long nr, int top_k, long long id_base, float* d_dist,
+                                         long long* d_ids, const unsigned int* d_keep) {
+    const Probe pr{d_range_ptr, d_ranges, nr, true};
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, &pr, top_k, id_base, d_dist, d_ids,
+                        nullptr, d_keep);
+}
+
+int pqh_search_stream_lists_masked(pqh_ctx_t* ctx, const pqh_tables_t* t,
+                                   const unsigned char* d_stream, unsigned long long stream_bytes,
+                                   long long n, int raw_first, int chunk_vectors,
+                                   const unsigned long long* d_chunk_offsets,
+                                   const void* d_chunk_prev, const long long* d_offsets,
+                                   long long nlist, const long long* d_probes, long long nq,
+                                   int nprobe, const float* d_lut, int tables_per_probe, int top_k,
+                                   long long id_base, float* d_dist, long long* d_ids,
+                                   const unsigned int* d_keep) {
+    const ListProbe ls{d_offsets, nlist, d_probes, nprobe, tables_per_probe != 0};
+    return search_stream(ctx, t, d_stream, stream_bytes, n, raw_first, chunk_vectors,
+                         d_chunk_offsets, d_chunk_prev, d_lut, nq, nullptr, top_k, id_base, d_dist,
+                         d_ids, &ls, d_keep);
+}
+
+int pqh_search_codes_lists_masked(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                                  const long long* d_offsets, long long nlist,
+                                  const long long* d_probes, long long nq, int nprobe,
+                                  const float* d_lut, int tables_per_probe, int top_k,
+                                  long long id_base, float* d_dist, long long* d_ids,
+                                  const unsigned int* d_keep) {
+    const ListProbe ls{d_offsets, nlist, d_probes, nprobe, tables_per_probe != 0};
+    return search_codes(ctx, d_codes, n, m, k, d_lut, nq, nullptr, top_k, id_base, d_dist, d_ids,
+                        &ls, d_keep);
 }
 
 }  // extern "C"
