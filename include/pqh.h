@@ -663,6 +663,57 @@ int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n], nonzero = 
  * read, like pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
 
+/* ---- refinement codes: a second compressed stream and a fused re-rank -------------------
+ * A row is stored twice: as the PQ code a of the vector (level 1, the stream the searches
+ * scan) and as the PQ code b of what level 1 left over, x - reconstruction (level 2, a stream
+ * of its own with its own tables and chunk index).  A search's candidates are re-ranked by
+ *   y = concat_i cent1[i][a_i] + concat_i cent2[i][b_i]      (one add per dimension)
+ *   t = q - y         (residual index: t = (q - c[l]) - y, l the list of the row)
+ *   dist = sum_j t[j] * t[j]
+ * in fp32, j ascending over all d = m1 * dsub1 = m2 * dsub2 dimensions as ONE chain (m1 and m2
+ * may differ), no contraction: the arithmetic of pqh_coarse_assign.  The list of stream row r
+ * is the last l with d_offsets[l] <= r, so empty lists are passed over.
+ * For each query q < nq: of the candidates d_rows[q][0 .. ncand) (int64 stream rows; -1 is
+ * padding and never an error; a row may be given twice and then appears twice) the top_k
+ * smallest by (dist, row) ascending, padded with (+inf, -1), into d_dist[q][0 .. top_k) and
+ * d_ids[q][0 .. top_k); the rows of both outputs are ld_out >= top_k elements apart and what
+ * lies between them is left alone.  1 <= ncand <= PQH_SEARCH_MAX_K, 1 <= top_k <= ncand.
+ * Query rows are ld_q >= d floats apart.  (cq, d_offsets): the coarse quantizer and the
+ * int64 [nlist + 1] list offsets of a residual index, both NULL for a plain one.
+ * Conventions of the search calls: device pointers, asynchronous on the context's stream; a
+ * NULL context returns PQH_ERR_NO_DEVICE when no HIP device is visible and PQH_ERR_ARG
+ * otherwise, checked before anything else.  PQH_ERR_ARG: a null pointer, the two levels (or
+ * cq) disagreeing in d, tables and codebook of a level disagreeing in m or K, ncand or top_k
+ * out of range, only one of cq and d_offsets given.  PQH_ERR_UNSUPPORTED: m > 16 or K > 256 at
+ * either level, d > PQH_ADC_RESIDUAL_MAX_D (the query row is staged in LDS), nq >= 2^31.  Any
+ * dsub, d need not be a multiple of four.  nq == 0 launches nothing.
+ * Errors on the device are pqh_decode_select's, reported by pqh_decode_status: a row outside
+ * [0, n) other than -1 (or, with d_offsets, at or past d_offsets[nlist]) is dropped and gives
+ * PQH_ERR_ARG; a chunk offset or a symbol past stream_bytes * 8 bits or an invalid code at
+ * either level drops that candidate and gives PQH_ERR_CORRUPT, which takes precedence.  Only
+ * the chunks of the candidates are read, and nothing outside stream_bytes at either level.
+ * Results for NaN inputs are unspecified.  Tree-mode streams are out of scope. */
+/* Both levels read from their streams: per level the tables, the codebook and the stream and
+ * index arguments of pqh_fetch_vectors (chunk sizes and context modes are independent). */
+int pqh_refine_stream(pqh_ctx_t* ctx, const pqh_tables_t* t1, const pqh_pq_t* pq1,
+                      const unsigned char* d_stream1, unsigned long long stream_bytes1,
+                      int raw_first1, int chunk_vectors1,
+                      const unsigned long long* d_chunk_offsets1, const void* d_chunk_prev1,
+                      const pqh_tables_t* t2, const pqh_pq_t* pq2, const unsigned char* d_stream2,
+                      unsigned long long stream_bytes2, int raw_first2, int chunk_vectors2,
+                      const unsigned long long* d_chunk_offsets2, const void* d_chunk_prev2,
+                      long long n, const pqh_coarse_t* cq, const long long* d_offsets,
+                      const float* d_queries, long long nq, long long ld_q,
+                      const long long* d_rows /* [nq][ncand] */, int ncand, int top_k,
+                      float* d_dist, long long* d_ids, long long ld_out);
+/* The same over plain row-major u8 codes [n][m1] and [n][m2]: the yardstick of the stream form,
+ * as pqh_search_codes is of the scan.  A code >= K drops the candidate (PQH_ERR_CORRUPT). */
+int pqh_refine_codes(pqh_ctx_t* ctx, const pqh_pq_t* pq1, const void* d_codes1,
+                     const pqh_pq_t* pq2, const void* d_codes2, long long n,
+                     const pqh_coarse_t* cq, const long long* d_offsets, const float* d_queries,
+                     long long nq, long long ld_q, const long long* d_rows /* [nq][ncand] */,
+                     int ncand, int top_k, float* d_dist, long long* d_ids, long long ld_out);
+
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by
  * the reference encoder) with a sequential table walk on the HOST copy of the stream
  * (index building only; the symbols themselves are decoded on the GPU). */

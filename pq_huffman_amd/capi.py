@@ -186,6 +186,11 @@ SIGNATURES = [
     ("pqh_search_codes_lists_masked", I,
      [P, P, LL, I, I, P, LL, P, LL, I, P, I, I, LL, P, P, P]),
     ("pqh_mask_pack", I, [P, P, P, LL, P]),
+    # per level (tables, pq, stream, bytes, raw_first, chunk_vectors, offsets, prev), then n
+    ("pqh_refine_stream", I,
+     [P, P, P, P, ULL, I, I, P, P, P, P, P, ULL, I, I, P, P, LL, P, P, P, LL, LL, P, I, I, P, P,
+      LL]),
+    ("pqh_refine_codes", I, [P, P, P, P, P, LL, P, P, P, LL, LL, P, I, I, P, P, LL]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

@@ -22,12 +22,15 @@ calls on device-resident data:
                          the queries that probe it (IVF.search(schedule="list"))
     pack_mask, keep=     filtered search: a bit per stream row, rows and chunks that are not kept
                          are not decoded (IVF.search(keep=...), IVF.remove)
+    refine, pq_residuals a second, finer code of what the first quantizer left over, as a stream
+                         of its own, and the fused re-rank of a search's candidates with both
+                         (IVF.build(refine_pq=...), IVF.search(refine=64), IVF.fetch(refined=True))
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
 (a sort and gathers of int64 in plain torch; Coarse.layout and Coarse.probe are their libpqh
-forms), IVF's gathers through its permutation and the centroid a residual IVF's fetch adds
-back (one torch add, not a hot path).  Device buffers are torch tensors owned by
+forms), IVF's gathers through its permutation, the centroid a residual IVF's fetch adds
+back and the subtract of pq_residuals (one torch add or sub_ each, not a hot path).  Device buffers are torch tensors owned by
 the caller.
 """
 from __future__ import annotations
@@ -617,6 +620,67 @@ def fetch(ctx: Context, tables: Tables, pq: PQ, enc: Encoded, ids, out=None):
     return out
 
 
+def pq_residuals(ctx: Context, pq: PQ, x, codes=None):
+    """what `pq` leaves over: x - pq.reconstruct(pq.assign(x)), float32 (n, m * dsub), one fp32
+    subtract per element (codes: the assignment, where the caller has it already).  The rows a
+    refinement codebook is trained on (IVF.build(refine_pq=...))."""
+    if codes is None:
+        codes = pq.assign(x, ctx=ctx)
+    return x[:, :pq.m * pq.dsub].clone().sub_(pq.reconstruct(codes))
+
+
+def _refine_level(level):
+    """(is a stream, n, the level's arguments in pqh.h order) of (tables, pq, enc) or (pq, codes)"""
+    if len(level) == 3:
+        tables, pq, enc = level
+        return True, enc.n, (tables.ptr, pq.ptr, _ptr(enc.stream), enc.stream.numel(),
+                             enc.raw_first, enc.chunk_vectors, _ptr(enc.chunk_offsets),
+                             _ptr(enc.chunk_prev))
+    pq, codes = level
+    if codes.dtype != _torch().uint8 or not codes.is_contiguous() or codes.shape[1] != pq.m:
+        raise PqhError(-1, "refine: codes is a contiguous uint8 tensor of shape (n, m)")
+    return False, codes.shape[0], (pq.ptr, _ptr(codes))
+
+
+def refine(ctx: Context, level1, level2, queries, rows, k: int, coarse: "Coarse" = None,
+           offsets=None, out=None):
+    """(dist, rows), each (nq, k): the candidates rows[q] (device int64 (nq, ncand), stream rows,
+    -1 = padding, ncand <= 64) of every query re-ranked by the distance to the sum of both
+    levels' reconstructions, ||q - (c1[a] + c2[b])||^2 in fp32 over all d dimensions in order;
+    the k <= ncand smallest by (dist, row), padded with (+inf, -1).  A level is (tables, pq, enc)
+    -- its row is decoded from the stream inside the kernel (pqh_refine_stream) -- or
+    (pq, codes) with plain uint8 codes (pqh_refine_codes); both levels in the same form.
+    coarse, offsets: the quantizer and the list offsets of a residual index (the query then
+    loses the centroid of the row's list first).  out: a (dist, rows) pair to fill, rows
+    out[0].stride(0) apart in both.  Async; decode_status reports a row outside [0, n)
+    (dropped) and a corrupt stream."""
+    torch = _torch()
+    s1, n1, a1 = _refine_level(level1)
+    s2, n2, a2 = _refine_level(level2)
+    if s1 != s2 or n1 != n2:
+        raise PqhError(-1, "refine: both levels as streams or both as codes, of the same rows")
+    if rows.dtype != torch.int64 or rows.dim() != 2 or not rows.is_contiguous() or \
+            rows.shape[0] != queries.shape[0]:
+        raise PqhError(-1, "refine: rows is a contiguous int64 tensor of shape (nq, ncand)")
+    if (coarse is None) != (offsets is None):
+        raise PqhError(-1, "refine: coarse and offsets go together")
+    nq, ncand = rows.shape
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=queries.device),
+               torch.empty((nq, k), dtype=torch.int64, device=queries.device))
+    dist, ids = out
+    ld = dist.stride(0) if nq > 1 else max(k, 1)
+    if nq > 1 and ids.stride(0) != ld or (k > 1 and (dist.stride(1) != 1 or ids.stride(1) != 1)):
+        raise PqhError(-1, "refine: out is a pair of tensors with rows the same distance apart")
+    tail = (n1, coarse.ptr if coarse is not None else None, _ptr(offsets), _ptr(queries), nq,
+            queries.stride(0), _ptr(rows), ncand, k, _ptr(dist), _ptr(ids), ld)
+    if s1:
+        check(lib().pqh_refine_stream(ctx.ptr, *a1, *a2, *tail), "pqh_refine_stream")
+    else:
+        check(lib().pqh_refine_codes(ctx.ptr, *a1, *a2, *tail), "pqh_refine_codes")
+    return dist, ids
+
+
 def adc_tables(ctx: Context, pq: PQ, queries, out=None):
     """the ADC tables of `queries` (device float32 (nq, >= m * dsub)): float32 (nq, m, K),
     lut[q][i][c] = ||q_i - cent[i][c]||^2 in the assignment's arithmetic (pqh_adc_tables)."""
@@ -978,8 +1042,14 @@ class IVF:
     bit per stream row that the scan reads before it decodes: a chunk without a kept row is not
     decoded, a list without one costs the read of its mask words.
 
+    refine_pq (IVFPQR): a second codebook over what `pq` leaves over of a row (train it on
+    pq_residuals of the rows the first one codes) gives every row a second code, kept as a
+    stream of its own (refine_tables, refine_enc).  search(refine=c) then takes the c <= 64 best
+    rows of the scan and returns the k best of them by the distance to the sum of both
+    reconstructions (codec.refine); fetch(refined=True) returns that sum.
+
     Every stage is a call on the context's stream.  search() never waits for the device;
-    build() waits where encode() does, once, for the stream's length."""
+    build() waits where encode() does, once per stream, for the stream's length."""
 
     table_budget = 256 << 20   # bytes of per-(query, list) tables a residual search holds at once
     # schedule="auto": list-major from nq * nprobe >= list_major_ratio * nlist on.  Measured at
@@ -993,31 +1063,51 @@ class IVF:
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
         self.perm, self.inv, self.offsets = perm, inv, offsets
         self.residual = residual
+        self.refine_pq = self.refine_tables = self.refine_enc = None   # build(refine_pq=...)
         self.live = None         # remove(): device bool per stream row, allocated on first use
         self._live_words = None  # its packed form, made again after a remove()
 
     @classmethod
     def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
-              context: bool = True, residual: bool = False) -> "IVF":
+              context: bool = True, residual: bool = False, refine_pq: PQ = None,
+              refine_chunk_vectors: int = None) -> "IVF":
         """x: device float32 (n, d), d = coarse.d = pq.m * pq.dsub.  The stages: rows to
         lists, layout, gather x[perm] (residual: coarse.residuals(x, lists, perm) in its
-        place), pq.assign, histogram, Tables.build, encode."""
+        place), pq.assign, histogram, Tables.build, encode.  refine_pq: what pq leaves over
+        (rows - pq.reconstruct(codes), in place) goes through the same four stages with
+        refine_pq, in chunks of refine_chunk_vectors (default: chunk_vectors)."""
         torch = _torch()
         if pq.k > 256 or pq.m > 16:
             raise PqhError(-4, "IVF.build: the search takes K <= 256 and m <= 16")
         if coarse.d != pq.m * pq.dsub or x.shape[1] != coarse.d:
             raise PqhError(-1, "IVF.build: x, the coarse centroids and the PQ disagree in d")
+        if refine_pq is not None:
+            if refine_pq.k > 256 or refine_pq.m > 16:
+                raise PqhError(-4, "IVF.build: the re-rank takes K <= 256 and m <= 16")
+            if refine_pq.m * refine_pq.dsub != coarse.d:
+                raise PqhError(-1, "IVF.build: refine_pq and the PQ disagree in d")
         lists = coarse.assign(x)
         perm, offsets = coarse.layout(lists)
         rows = coarse.residuals(x, lists, perm) if residual else x[perm]
         codes = pq.assign(rows, ctx=ctx)
+        refined = None
+        if refine_pq is not None:
+            rows.sub_(pq.reconstruct(codes))
+            codes2 = refine_pq.assign(rows, ctx=ctx)
+            tables2 = Tables(ctx, refine_pq.m, refine_pq.k, context).build(
+                histogram(ctx, codes2, refine_pq.k, context))
+            refined = (tables2, encode(ctx, tables2, codes2,
+                                       chunk_vectors=refine_chunk_vectors or chunk_vectors))
         del rows
         counts = histogram(ctx, codes, pq.k, context)
         tables = Tables(ctx, pq.m, pq.k, context).build(counts)
         enc = encode(ctx, tables, codes, chunk_vectors=chunk_vectors)
         inv = torch.empty_like(perm)
         inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
-        return cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
+        ivf = cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
+        if refined is not None:
+            ivf.refine_pq, (ivf.refine_tables, ivf.refine_enc) = refine_pq, refined
+        return ivf
 
     def remove(self, ids) -> None:
         """take the caller rows `ids` (device int64, each in [0, n)) out of every later search,
@@ -1045,7 +1135,8 @@ class IVF:
         words = pack_mask(self.ctx, keep, self.perm)
         return words if self._live_words is None else words & self._live_words
 
-    def search(self, queries, nprobe: int, k: int, schedule: str = "query", keep=None):
+    def search(self, queries, nprobe: int, k: int, schedule: str = "query", keep=None,
+               refine: int = 0):
         """(dist, ids), each (nq, k): the k nearest rows by ADC distance among the rows of each
         query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1).
         schedule: "query" decodes a list once for every query that probes it (search_ranges),
@@ -1053,16 +1144,27 @@ class IVF:
         from nq * nprobe >= list_major_ratio * nlist on; the result is the same bits.
         keep: device bool (n,) over the caller's rows of x: only rows with keep[id] set are
         returned -- the k nearest among them, not the kept ones of the k nearest.  Rows taken
-        out by remove() are never returned."""
+        out by remove() are never returned.
+        refine: 0, or the number c of candidates, k <= c <= 64, on an index built with
+        refine_pq: the scan returns its c best rows and the k best of those by the refined
+        distance (both levels' reconstructions added, codec.refine) are the result, their
+        distances the refined ones."""
         torch = _torch()
         if schedule not in ("query", "list", "auto"):
             raise PqhError(-1, f"IVF.search: schedule {schedule!r}")
+        if refine:
+            if self.refine_pq is None:
+                raise PqhError(-1, "IVF.search: refine > 0 on an index built without refine_pq")
+            if not k <= refine <= 64:
+                raise PqhError(-1, f"IVF.search: refine = {refine} outside [k, 64]")
+            top_k, k = k, refine
         by_list = schedule == "list" or (
             schedule == "auto" and
             queries.shape[0] * nprobe >= self.list_major_ratio * self.coarse.nlist)
         mask = self._mask(keep)
         if self.residual:
-            dist, rows = self._search_residual(queries, nprobe, k, by_list, mask)
+            dist, rows = self._search_residual(queries, nprobe, k, by_list, mask,
+                                               top_k if refine else 0)
             return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
         lut = adc_tables(self.ctx, self.pq, queries)
         range_ptr, ranges, probes, _ = self.coarse.probe(queries, nprobe, self.offsets,
@@ -1073,18 +1175,32 @@ class IVF:
         else:
             dist, rows = search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
                                        keep=mask)
+        if refine:
+            dist, rows = self._refine(queries, rows, top_k)
         return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
 
-    def _search_residual(self, queries, nprobe: int, k: int, by_list: bool = False, mask=None):
+    def _refine(self, queries, rows, k: int, out=None):
+        """(dist, stream rows): the k best of the scan's candidate rows by both levels' codes"""
+        return refine(self.ctx, (self.tables, self.pq, self.enc),
+                      (self.refine_tables, self.refine_pq, self.refine_enc), queries, rows, k,
+                      self.coarse if self.residual else None,
+                      self.offsets if self.residual else None, out=out)
+
+    def _search_residual(self, queries, nprobe: int, k: int, by_list: bool = False, mask=None,
+                         refine_k: int = 0):
         """(dist, stream rows): probe, one table per (query, list), the probe search with a
         table per range (by_list: per pair, list-major) -- slab by slab, the table buffer reused;
-        mask: the words of the rows that may be returned, the same for every slab"""
+        mask: the words of the rows that may be returned, the same for every slab; refine_k > 0:
+        every slab's k candidates re-ranked to refine_k results"""
         torch = _torch()
         nq = queries.shape[0]
         per_query = nprobe * self.pq.m * self.pq.k * 4
         slab = max(1, min(max(nq, 1), int(self.table_budget) // per_query))
         dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
         rows = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+        if refine_k:
+            fine = (torch.empty((nq, refine_k), dtype=torch.float32, device=queries.device),
+                    torch.empty((nq, refine_k), dtype=torch.int64, device=queries.device))
         lut = torch.empty((slab * nprobe, self.pq.m, self.pq.k), dtype=torch.float32,
                           device=queries.device)
         for s in range(0, nq, slab):
@@ -1099,16 +1215,25 @@ class IVF:
             else:
                 search_range_tables(self.ctx, self.tables, self.enc, lut, range_ptr, ranges, k,
                                     out=out, keep=mask)
-        return dist, rows
+            if refine_k:
+                self._refine(q, out[1], refine_k, out=(fine[0][s:s + slab], fine[1][s:s + slab]))
+        return fine if refine_k else (dist, rows)
 
-    def fetch(self, ids, out=None):
-        """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)), for
-        an exact re-rank (fetch through the inverse permutation; residual: the decoded
-        residual plus the centroid of the stream row's list, one fp32 add).  remove() does not
-        affect it: the stream still holds a removed row."""
+    def fetch(self, ids, out=None, refined: bool = False):
+        """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)): what
+        the index knows of them (fetch through the inverse permutation; residual: the decoded
+        residual plus the centroid of the stream row's list, one fp32 add).  refined=True, on an
+        index built with refine_pq: the level-2 reconstruction is fetched too and added first,
+        (c1 + c2) and then + centroid -- the vectors search(refine=...) measures against.
+        remove() does not affect it: the stream still holds a removed row."""
         torch = _torch()
+        if refined and self.refine_pq is None:
+            raise PqhError(-1, "IVF.fetch: refined=True on an index built without refine_pq")
         rows = self.inv[ids.reshape(-1)]
         out = fetch(self.ctx, self.tables, self.pq, self.enc, rows, out)
+        if refined:
+            out[:, :self.coarse.d] += fetch(self.ctx, self.refine_tables, self.refine_pq,
+                                            self.refine_enc, rows)
         if self.residual:
             # (right=True passes over the empty lists that end where the row's list begins)
             lists = torch.searchsorted(self.offsets[1:].contiguous(), rows, right=True)

@@ -89,6 +89,9 @@ int pqh_pq_error_accum(pqh_ctx* ctx, const pqh_pq_t* pq, const float* d_x, long 
 // a prepared codebook's shape and its device centroids [m][k][dsub] (pqh_assign.hip), for the
 // fused reconstruction of pqh_fetch_vectors; PQH_ERR_ARG for a null codebook
 int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_cent);
+// a coarse quantizer's shape and its device centroids [nlist][d] (pqh_ivf.hip), for the re-rank
+// of a residual index (pqh_refine.hip); PQH_ERR_ARG for a null quantizer
+int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_cent);
 // pqh_shard_encode's histogram / size / write with this shard's raw-first flag in device
 // memory (1: row 0 raw, no halo pair; 0: row 0 in the context of d_prev_row) -- pqh_huff.hip
 extern "C" {

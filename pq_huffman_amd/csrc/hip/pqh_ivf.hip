@@ -371,6 +371,14 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
+int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_cent) {
+    if (!cq) return PQH_ERR_ARG;
+    *nlist = cq->nlist;
+    *d = cq->d;
+    *d_cent = cq->d_cent;
+    return PQH_OK;
+}
+
 extern "C" {
 
 int pqh_coarse_create(pqh_ctx_t* ctx, const float* centroids, int nlist, int d, pqh_coarse_t** cq) {
