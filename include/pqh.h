@@ -341,14 +341,25 @@ int pqh_fetch_vectors(pqh_ctx_t* ctx, const pqh_tables_t* t, const pqh_pq_t* pq,
  * Device pointers, asynchronous on the context's stream.  A NULL context -- all a process
  * without a GPU can have -- returns PQH_ERR_NO_DEVICE when no HIP device is visible and
  * PQH_ERR_ARG otherwise; that check comes first, every other argument check after it.
- * PQH_ERR_ARG: a null pointer, top_k < 1 or > PQH_SEARCH_MAX_K, chunk_vectors < 1, a
- * negative count.  PQH_ERR_UNSUPPORTED: K > 256 (a K = 4096 table is 128 KB per query: no
+ * PQH_ERR_ARG: a null pointer, top_k < 1 or > the context's limit (PQH_SEARCH_MAX_K unless
+ * pqh_ctx_set_search_max_k raised it), chunk_vectors < 1, a negative count.  PQH_ERR_UNSUPPORTED: K > 256 (a K = 4096 table is 128 KB per query: no
  * batch of them fits the LDS), m > 16, a chunk of more than ~90 KB of codes (C * m).
  * Tree-mode streams are out of scope, as for random access.  nq == 0 launches nothing; n == 0
  * fills the outputs with the padding.  The tables may hold any finite floats (negative ones,
  * inner products); the result for NaN entries is unspecified.
  * Scratch: 12 bytes * nq * top_k per workgroup of the scan grid, in the context workspace. */
 #define PQH_SEARCH_MAX_K 64
+/* The limit of top_k (and of pqh_refine_*'s ncand) is the context's: PQH_SEARCH_MAX_K for a new
+ * context, up to PQH_SEARCH_MAX_K_WIDE after pqh_ctx_set_search_max_k (64 <= max_k <= 256,
+ * else PQH_ERR_ARG).  Calls with top_k <= 64 launch the same kernels whatever the limit is;
+ * above 64 a scan keeps four entries a lane (a list of 256 per wave), scores four queries a
+ * workgroup at the most, and the scratch grows with top_k as stated above.  The results have
+ * the same definition at every width.  Not a pqh_ctx_set_tuning key: tuning never changes
+ * what a call returns, and this changes which calls are accepted.  pqh_ctx_search_max_k
+ * returns the limit.  A NULL context answers as in the search calls. */
+#define PQH_SEARCH_MAX_K_WIDE 256
+int pqh_ctx_set_search_max_k(pqh_ctx_t* ctx, int max_k);
+int pqh_ctx_search_max_k(const pqh_ctx_t* ctx);
 
 /* lut[q][i][c] = sum_j (query[q][i*dsub+j] - cent[i][c][j])^2: fp32, j order, no contraction
  * (the oracle arithmetic of pqh_pq_assign).  d_lut: device float [nq][m][K].  K <= 256.
@@ -677,7 +688,8 @@ int pqh_ivf_status(pqh_ctx_t* ctx);
  * padding and never an error; a row may be given twice and then appears twice) the top_k
  * smallest by (dist, row) ascending, padded with (+inf, -1), into d_dist[q][0 .. top_k) and
  * d_ids[q][0 .. top_k); the rows of both outputs are ld_out >= top_k elements apart and what
- * lies between them is left alone.  1 <= ncand <= PQH_SEARCH_MAX_K, 1 <= top_k <= ncand.
+ * lies between them is left alone.  1 <= ncand <= the context's limit (PQH_SEARCH_MAX_K, or what
+ * pqh_ctx_set_search_max_k set, 256 at the most), 1 <= top_k <= ncand.
  * Query rows are ld_q >= d floats apart.  (cq, d_offsets): the coarse quantizer and the
  * int64 [nlist + 1] list offsets of a residual index, both NULL for a plain one.
  * Conventions of the search calls: device pointers, asynchronous on the context's stream; a

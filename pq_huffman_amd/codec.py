@@ -119,6 +119,20 @@ class Context:
                   f"pqh_ctx_set_tuning({key})")
         return self
 
+    def set_search_max_k(self, max_k: int) -> "Context":
+        """the largest k of the searches and candidate count of refine() this context accepts
+        (pqh_ctx_set_search_max_k): 64 for a new context, up to 256.  Calls with k <= 64 run
+        the same kernels whatever the limit; above 64 the scans keep a list of 256 a wave."""
+        check(lib().pqh_ctx_set_search_max_k(self.ptr, int(max_k)), "pqh_ctx_set_search_max_k")
+        return self
+
+    @property
+    def search_max_k(self) -> int:
+        limit = lib().pqh_ctx_search_max_k(self.ptr)
+        if limit < 0:
+            raise PqhError(limit, "pqh_ctx_search_max_k")
+        return limit
+
     def sync(self) -> None:
         check(lib().pqh_ctx_sync(self.ptr), "pqh_ctx_sync")
 
@@ -645,7 +659,7 @@ def _refine_level(level):
 def refine(ctx: Context, level1, level2, queries, rows, k: int, coarse: "Coarse" = None,
            offsets=None, out=None):
     """(dist, rows), each (nq, k): the candidates rows[q] (device int64 (nq, ncand), stream rows,
-    -1 = padding, ncand <= 64) of every query re-ranked by the distance to the sum of both
+    -1 = padding, ncand <= ctx.search_max_k) of every query re-ranked by the distance to the sum of both
     levels' reconstructions, ||q - (c1[a] + c2[b])||^2 in fp32 over all d dimensions in order;
     the k <= ncand smallest by (dist, row), padded with (+inf, -1).  A level is (tables, pq, enc)
     -- its row is decoded from the stream inside the kernel (pqh_refine_stream) -- or
@@ -1045,7 +1059,7 @@ class IVF:
     refine_pq (IVFPQR): a second codebook over what `pq` leaves over of a row (train it on
     pq_residuals of the rows the first one codes) gives every row a second code, kept as a
     stream of its own (refine_tables, refine_enc).  search(refine=c) then takes the c <= 64 best
-    rows of the scan and returns the k best of them by the distance to the sum of both
+    (c <= 256 after ctx.set_search_max_k(256)) rows of the scan and returns the k best of them by the distance to the sum of both
     reconstructions (codec.refine); fetch(refined=True) returns that sum.
 
     Every stage is a call on the context's stream.  search() never waits for the device;
@@ -1145,7 +1159,8 @@ class IVF:
         keep: device bool (n,) over the caller's rows of x: only rows with keep[id] set are
         returned -- the k nearest among them, not the kept ones of the k nearest.  Rows taken
         out by remove() are never returned.
-        refine: 0, or the number c of candidates, k <= c <= 64, on an index built with
+        refine: 0, or the number c of candidates, k <= c <= ctx.search_max_k, on an index built
+        with
         refine_pq: the scan returns its c best rows and the k best of those by the refined
         distance (both levels' reconstructions added, codec.refine) are the result, their
         distances the refined ones."""
@@ -1155,8 +1170,9 @@ class IVF:
         if refine:
             if self.refine_pq is None:
                 raise PqhError(-1, "IVF.search: refine > 0 on an index built without refine_pq")
-            if not k <= refine <= 64:
-                raise PqhError(-1, f"IVF.search: refine = {refine} outside [k, 64]")
+            limit = self.ctx.search_max_k
+            if not k <= refine <= limit:
+                raise PqhError(-1, f"IVF.search: refine = {refine} outside [k, {limit}]")
             top_k, k = k, refine
         by_list = schedule == "list" or (
             schedule == "auto" and

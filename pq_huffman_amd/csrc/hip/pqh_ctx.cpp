@@ -249,6 +249,17 @@ int pqh_ctx_set_tuning(pqh_ctx_t* ctx, int key, double value) {
     }
 }
 
+int pqh_ctx_set_search_max_k(pqh_ctx_t* ctx, int max_k) {
+    if (!ctx) return pqh_no_ctx_status();
+    if (max_k < PQH_SEARCH_MAX_K || max_k > PQH_SEARCH_MAX_K_WIDE) return PQH_ERR_ARG;
+    ctx->search_max_k = max_k;
+    return PQH_OK;
+}
+
+int pqh_ctx_search_max_k(const pqh_ctx_t* ctx) {
+    return ctx ? ctx->search_max_k : pqh_no_ctx_status();
+}
+
 int pqh_ctx_sync(pqh_ctx_t* ctx) {
     if (!ctx) return PQH_ERR_ARG;
     PQH_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -55,6 +55,8 @@ struct pqh_ctx {
     int tune_hist_block = 0;
     int tune_enc_impl = 0;   // 1 tiled, 2 one-pass (0: PQH_ENC_IMPL or tiled)
     int tune_search_groups = 0;   // workgroups per query batch of the ADC scan (0: from num_cus)
+    // pqh_ctx_set_search_max_k: the largest top_k / ncand the search and re-rank calls accept
+    int search_max_k = PQH_SEARCH_MAX_K;
     // the tiled encoder's scratch: one worst-case slot per tile (grow-only)
     void* enc_scr = nullptr;
     size_t enc_scr_bytes = 0;

@@ -22,6 +22,9 @@
 //                Errors are sel_rows': bit 1 for a chunk offset or a symbol past the stream or
 //                an invalid code (the candidate takes no part), bit 2 for a row outside [0, n)
 //                but the padding -1 (or a row past the last list of a residual index).
+//  refine_rows_wide  the same for 64 < ncand <= 256 (a context whose limit was raised): a wave
+//                pair per 64 candidates, up to eight waves, the keys sorted through the wide
+//                list of pqh_topk_dev.h.
 #include <cmath>
 
 #include "pqh_decode_dev.h"
@@ -178,6 +181,144 @@ refine_rows(Levels P, long long n, const float* __restrict__ coarse, int nlist,
     }
 }
 
+// refine_rows' distance phase for the wide kernel (refine_rows keeps its own text, and so its
+// code): the distance of candidate row v, its code rows a and b in LDS, one chain over the d
+// dimensions.  *valid is cleared (and error bit 2 set) for a row past the last list of a
+// residual index.
+__device__ __forceinline__ float cand_dist(const Levels& P, const float* coarse, int nlist,
+                                           const long long* offsets, const float* qs, int d,
+                                           long long v, const uint8_t* a, const uint8_t* b,
+                                           bool& valid, unsigned long long* err) {
+    const float* __restrict__ cl = nullptr;   // residual index: the centroid of the row's list
+    if (coarse && valid) {
+        // the last list with offsets[l] <= v: the entries of offsets[1 ... nlist] that are <= v
+        int lo = 0, hi = nlist;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (offsets[1 + mid] <= v) lo = mid + 1; else hi = mid;
+        }
+        if (lo >= nlist) {   // (a row past the last list: the offsets do not cover the stream)
+            valid = false;
+            atomicOr(err, 2ull);
+        }
+        cl = coarse + (long long)lo * d;
+    }
+    float acc = 0.f;
+    if (valid) {
+        const int ds1 = P.lv[0].dsub, ds2 = P.lv[1].dsub;
+        const long long k1 = P.lv[0].k, k2 = P.lv[1].k;
+        const float* __restrict__ cent1 = P.lv[0].cent;
+        const float* __restrict__ cent2 = P.lv[1].cent;
+        const bool vec = !((ds1 | ds2) & 3) &&
+                         !((reinterpret_cast<uintptr_t>(cent1) | reinterpret_cast<uintptr_t>(cent2) |
+                            reinterpret_cast<uintptr_t>(coarse)) & 15u);
+        int i1 = 0, j1 = 0, i2 = 0, j2 = 0;
+        const float* c1 = cent1 + (long long)a[0] * ds1;
+        const float* c2 = cent2 + (long long)b[0] * ds2;
+        if (vec) {   // every sub-vector a multiple of four floats: the same sum, 16-byte loads
+            for (int j = 0; j < d; j += 4) {
+                const float4 u1 = *reinterpret_cast<const float4*>(c1 + j1);
+                const float4 u2 = *reinterpret_cast<const float4*>(c2 + j2);
+                float4 x = *reinterpret_cast<const float4*>(qs + j);
+                if (cl) {
+                    const float4 cv = *reinterpret_cast<const float4*>(cl + j);
+                    x = make_float4(x.x - cv.x, x.y - cv.y, x.z - cv.z, x.w - cv.w);
+                }
+                const float t0 = x.x - (u1.x + u2.x), t1 = x.y - (u1.y + u2.y),
+                            t2 = x.z - (u1.z + u2.z), t3 = x.w - (u1.w + u2.w);
+                acc = acc + t0 * t0;
+                acc = acc + t1 * t1;
+                acc = acc + t2 * t2;
+                acc = acc + t3 * t3;
+                j1 += 4;
+                j2 += 4;
+                if (j1 == ds1 && j + 4 < d) ++i1, c1 = cent1 + (i1 * k1 + a[i1]) * ds1, j1 = 0;
+                if (j2 == ds2 && j + 4 < d) ++i2, c2 = cent2 + (i2 * k2 + b[i2]) * ds2, j2 = 0;
+            }
+        } else {
+            for (int j = 0; j < d; ++j) {
+                const float y = c1[j1] + c2[j2];
+                float x = qs[j];
+                if (cl) x = x - cl[j];
+                const float t = x - y;
+                acc = acc + t * t;
+                if (++j1 == ds1 && j + 1 < d) ++i1, c1 = cent1 + (i1 * k1 + a[i1]) * ds1, j1 = 0;
+                if (++j2 == ds2 && j + 1 < d) ++i2, c2 = cent2 + (i2 * k2 + b[i2]) * ds2, j2 = 0;
+            }
+        }
+    }
+    return acc;
+}
+
+// refine_rows for 64 < ncand <= 256: a wave pair per 64 candidates, so the pairs' row walks --
+// the whole cost over streams -- run side by side.  Wave 2p walks level 1 and wave 2p + 1 level
+// 2 of candidates [64p, 64p + 64); the even waves then compute their candidates' distances
+// (the same one chain), and wave 0 sorts the workgroup's keys through the wide list.  The
+// workgroup has 2 * ceil(ncand / 64) waves.
+constexpr int kWidePairs = PQH_SEARCH_MAX_K_WIDE / 64;
+static_assert(kWidePairs == kWideKR, "the wide list holds the candidates of every pair");
+template <bool STREAM>
+__global__ void __launch_bounds__(128 * kWidePairs)
+refine_rows_wide(Levels P, long long n, const float* __restrict__ coarse, int nlist,
+                 const long long* __restrict__ offsets, const float* __restrict__ queries,
+                 long long ld_q, const long long* __restrict__ rows, int ncand, int top_k,
+                 float* __restrict__ dist, long long* __restrict__ ids, long long ld_out,
+                 unsigned long long* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) float qs[];   // the query row, d floats
+    __shared__ __attribute__((aligned(4))) uint8_t code[2][64 * kWidePairs * kRowStride];
+    __shared__ unsigned char dead[2][64 * kWidePairs];
+    __shared__ float key_d[64 * kWidePairs];
+    __shared__ long long key_id[64 * kWidePairs];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lv = w & 1;
+    const int c = (w >> 1) * 64 + lane;   // the candidate: below 64 * pairs, the workgroup's waves
+    const long long q = blockIdx.x;
+    const int d = P.lv[0].m * P.lv[0].dsub;
+    const float* __restrict__ qrow = queries + q * ld_q;
+    for (int j = threadIdx.x; j < d; j += (int)blockDim.x) qs[j] = qrow[j];
+
+    // ---- decode: wave 2p + l walks level l
+    const long long v = c < ncand ? rows[q * ncand + c] : -1;
+    const bool inside = v >= 0 && v < n;
+    unsigned flag = (v < -1 || v >= n) ? 2u : 0u;
+    bool good = false;
+    if (inside) {
+        const Level L = lv ? P.lv[1] : P.lv[0];
+        good = level_row<STREAM>(L, v, &code[lv][c * kRowStride]);
+        if (!good) flag = 1;
+    }
+    dead[lv][c] = good ? 0 : 1;
+    if (flag && (lv == 0 || flag == 1)) atomicOr(err, (unsigned long long)flag);
+    lds_barrier();
+
+    // ---- distance: the even waves, one chain over the d dimensions each
+    if (lv == 0) {
+        bool valid = inside && !dead[0][c] && !dead[1][c];
+        const float acc = cand_dist(P, coarse, nlist, offsets, qs, d, v, &code[0][c * kRowStride],
+                                    &code[1][c * kRowStride], valid, err);
+        key_d[c] = valid ? acc : INFINITY;
+        key_id[c] = valid ? v : 0x7FFFFFFFFFFFFFFFll;
+    }
+    lds_barrier();
+    if (w) return;
+
+    // ---- select: the pairs' keys, 64 at a time, into the wide list
+    const int kth = ncand - 1;
+    TopKW e;
+    list_clear(e);
+#pragma unroll 1
+    for (int b = 0; b <= (kth >> 6); ++b)
+        list_merge<false>(e, TopK{key_d[b * 64 + lane], key_id[b * 64 + lane]}, kth);
+#pragma unroll
+    for (int b = 0; b < kWideKR; ++b) {
+        if (b * 64 + lane < top_k) {
+            dist[q * ld_out + b * 64 + lane] = e.d[b];
+            ids[q * ld_out + b * 64 + lane] = e.id[b];
+        }
+    }
+}
+
 // the arguments of one level as the entry points take them
 struct LevelArgs {
     const pqh_tables_t* t;
@@ -228,7 +369,7 @@ int refine(pqh_ctx_t* ctx, bool stream, const LevelArgs& a1, const LevelArgs& a2
            long long ld_q, const long long* d_rows, int ncand, int top_k, float* d_dist,
            long long* d_ids, long long ld_out) {
     if (!ctx) return pqh_no_ctx_status();
-    if (n < 0 || nq < 0 || ncand < 1 || ncand > PQH_SEARCH_MAX_K || top_k < 1 || top_k > ncand ||
+    if (n < 0 || nq < 0 || ncand < 1 || ncand > ctx->search_max_k || top_k < 1 || top_k > ncand ||
         ld_out < top_k || (cq != nullptr) != (d_offsets != nullptr))
         return PQH_ERR_ARG;
     const bool run = nq > 0;
@@ -251,14 +392,16 @@ int refine(pqh_ctx_t* ctx, bool stream, const LevelArgs& a1, const LevelArgs& a2
     if (!run) return PQH_OK;
     // (no memset: d_diag[1] is sticky until pqh_decode_status reads it)
     const size_t lds = (size_t)d * 4;
+    const bool wide = ncand > PQH_SEARCH_MAX_K;   // a wave pair per 64 candidates
+    const dim3 block(wide ? 128 * ((ncand + 63) / 64) : 128);
     if (stream)
-        hipLaunchKernelGGL(refine_rows<true>, dim3((unsigned)nq), dim3(128), lds, ctx->stream, P, n,
-                           d_coarse, nlist, d_offsets, d_queries, ld_q, d_rows, ncand, top_k,
-                           d_dist, d_ids, ld_out, ctx->d_diag + 1);
+        hipLaunchKernelGGL(wide ? refine_rows_wide<true> : refine_rows<true>, dim3((unsigned)nq),
+                           block, lds, ctx->stream, P, n, d_coarse, nlist, d_offsets, d_queries,
+                           ld_q, d_rows, ncand, top_k, d_dist, d_ids, ld_out, ctx->d_diag + 1);
     else
-        hipLaunchKernelGGL(refine_rows<false>, dim3((unsigned)nq), dim3(128), lds, ctx->stream, P, n,
-                           d_coarse, nlist, d_offsets, d_queries, ld_q, d_rows, ncand, top_k,
-                           d_dist, d_ids, ld_out, ctx->d_diag + 1);
+        hipLaunchKernelGGL(wide ? refine_rows_wide<false> : refine_rows<false>, dim3((unsigned)nq),
+                           block, lds, ctx->stream, P, n, d_coarse, nlist, d_offsets, d_queries,
+                           ld_q, d_rows, ncand, top_k, d_dist, d_ids, ld_out, ctx->d_diag + 1);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
 }

@@ -23,11 +23,17 @@
 //              the row may be returned.  A lane decodes its chunk as far as its last kept row
 //              (not at all without one), and a step without a kept row is passed over before
 //              its window, its rows or (RT) its table are loaded.
+//              KR = 4 (top_k > 64, a context whose limit pqh_ctx_set_search_max_k raised; every
+//              form above): the lists are pqh_topk_dev.h's wide ones, 256 entries a wave, four a
+//              lane.  At most four queries a workgroup (QB <= 4, LM's units with it) and eight
+//              waves: twelve more registers a query, and the waves' lists exchanged through LDS
+//              at the end are waves * QB * 256 * 12 bytes.  KR = 1 is the code it was.
 //  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
 //  lists_*     the probe list turned round for LM: the pairs of every list in CSR form
 //              (count, scan, fill), cut into work units of up to QB pairs.
 //  adc_merge   one workgroup per query: every scan workgroup's list through the same list code
-//              (pqh_topk_dev.h, shared with the probe selection of pqh_ivf.hip).
+//              (pqh_topk_dev.h, shared with the probe selection of pqh_ivf.hip); adc_merge_wide
+//              for top_k > 64.
 //
 // dist(v) = ((lut[0][c_0] + lut[1][c_1]) + ...) + lut[m-1][c_{m-1}] in fp32, the order total
 // (dist, then row id), so the result does not depend on the grid.
@@ -42,6 +48,7 @@
 namespace {
 
 constexpr int kScanWavesMax = 16;          // waves per workgroup (threadIdx.y; threadIdx.x = lane)
+constexpr int kWideWavesMax = 8;           // the same with the wide list (KR = kWideKR)
 constexpr int kLdsBytes = 160 * 1024;
 constexpr int kCodesRowsPerLane = 4;       // SRC = 1: a wave stages 64 * 4 rows per step
 constexpr int kRangeWaves = 4;             // the probe search: waves per workgroup, and how many
@@ -306,9 +313,10 @@ __global__ void __launch_bounds__(256) lists_fill(const ListArgs a) {
 }
 
 template <int SRC, int NW, bool CTX, int QB, bool RG = false, bool RT = false, bool LM = false,
-          bool FL = false>
-__global__ void __launch_bounds__(64 * kScanWavesMax)
+          bool FL = false, int KR = 1>
+__global__ void __launch_bounds__(64 * (KR == 1 ? kScanWavesMax : kWideWavesMax))
 adc_scan(const ScanArgs a) {
+    static_assert(KR == 1 || (KR == kWideKR && QB <= 4), "the wide list: four queries at the most");
     static_assert(RG == (QB == 1), "one query per workgroup is the probe search's form");
     static_assert(!RT || RG, "a table per range is a form of the probe search");
     static_assert(!LM || !RG, "the list-major form scores a batch of pairs");
@@ -396,9 +404,14 @@ adc_scan(const ScanArgs a) {
         steps = ((l_first + l_count - 1) / C - l_first / C + a.L) / a.L;
     }
 
-    TopK list[QB];
+    std::conditional_t<KR == 1, TopK, TopKW> list[QB];
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) list[qq] = TopK{INFINITY, -1ll};
+    for (int qq = 0; qq < QB; ++qq) {
+        if constexpr (KR == 1)
+            list[qq] = TopK{INFINITY, -1ll};
+        else
+            list_clear(list[qq]);
+    }
     const int kth = a.top_k - 1;
 
     const long long chunks = (a.n + C - 1) / C;
@@ -632,29 +645,67 @@ adc_scan(const ScanArgs a) {
     // The workgroup's lists into one per query: the tables and the stages are done with, so
     // every wave leaves its lists in LDS and wave w merges those of queries w, w + waves, ...
     lds_barrier();
-    float* ex_d = reinterpret_cast<float*>(lds);   // [waves][QB][64]
-    long long* ex_id = reinterpret_cast<long long*>(lds + (size_t)waves * QB * 64 * 4);
+    if constexpr (KR > 1) {
+        // the wide list: a wave's blocks side by side, each offered as the sorted 64 it is
+        float* wx_d = reinterpret_cast<float*>(lds);   // [waves][QB][KR][64]
+        long long* wx_id = reinterpret_cast<long long*>(lds + (size_t)waves * QB * KR * 64 * 4);
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-        ex_d[(wave * QB + qq) * 64 + lane] = list[qq].d;
-        ex_id[(wave * QB + qq) * 64 + lane] = list[qq].id;
-    }
-    lds_barrier();
-#pragma unroll 1
-    for (int qq = wave; qq < QB && (LM ? qq < u_cnt : q0 + qq < a.nq); qq += waves) {
-        TopK e{INFINITY, -1ll};
-#pragma unroll 1
-        for (int s = 0; s < waves; ++s) {
-            const float d = ex_d[(s * QB + qq) * 64 + lane];
-            const long long id = ex_id[(s * QB + qq) * 64 + lane];
-            list_offer<true>(e, d, id, id >= 0, kth);
+        for (int qq = 0; qq < QB; ++qq) {
+#pragma unroll
+            for (int b = 0; b < KR; ++b) {
+                wx_d[((wave * QB + qq) * KR + b) * 64 + lane] = list[qq].d[b];
+                wx_id[((wave * QB + qq) * KR + b) * 64 + lane] = list[qq].id[b];
+            }
         }
-        if (lane < a.top_k) {
-            // (LM: the pair's lists, one per group -- a group without steps leaves the padding)
+        lds_barrier();
+#pragma unroll 1
+        for (int qq = wave; qq < QB && (LM ? qq < u_cnt : q0 + qq < a.nq); qq += waves) {
+            TopKW e;
+            list_clear(e);
+#pragma unroll 1
+            for (int s = 0; s < waves; ++s) {
+#pragma unroll 1
+                for (int b = 0; b <= (kth >> 6); ++b) {
+                    const float d = wx_d[((s * QB + qq) * KR + b) * 64 + lane];
+                    const long long id = wx_id[((s * QB + qq) * KR + b) * 64 + lane];
+                    list_offer<true>(e, d, id, id >= 0, kth);
+                }
+            }
             const long long slot = LM ? (long long)a.pairs[u_first + qq] : q0 + qq;
-            const long long o = (slot * gridDim.y + blockIdx.y) * a.top_k + lane;
-            a.part_d[o] = e.d;
-            a.part_id[o] = e.id;
+            const long long o = (slot * gridDim.y + blockIdx.y) * a.top_k;
+#pragma unroll
+            for (int b = 0; b < KR; ++b) {
+                if (b * 64 + lane < a.top_k) {
+                    a.part_d[o + b * 64 + lane] = e.d[b];
+                    a.part_id[o + b * 64 + lane] = e.id[b];
+                }
+            }
+        }
+    } else {
+        float* ex_d = reinterpret_cast<float*>(lds);   // [waves][QB][64]
+        long long* ex_id = reinterpret_cast<long long*>(lds + (size_t)waves * QB * 64 * 4);
+#pragma unroll
+        for (int qq = 0; qq < QB; ++qq) {
+            ex_d[(wave * QB + qq) * 64 + lane] = list[qq].d;
+            ex_id[(wave * QB + qq) * 64 + lane] = list[qq].id;
+        }
+        lds_barrier();
+#pragma unroll 1
+        for (int qq = wave; qq < QB && (LM ? qq < u_cnt : q0 + qq < a.nq); qq += waves) {
+            TopK e{INFINITY, -1ll};
+#pragma unroll 1
+            for (int s = 0; s < waves; ++s) {
+                const float d = ex_d[(s * QB + qq) * 64 + lane];
+                const long long id = ex_id[(s * QB + qq) * 64 + lane];
+                list_offer<true>(e, d, id, id >= 0, kth);
+            }
+            if (lane < a.top_k) {
+                // (LM: the pair's lists, one per group -- a group without steps leaves the padding)
+                const long long slot = LM ? (long long)a.pairs[u_first + qq] : q0 + qq;
+                const long long o = (slot * gridDim.y + blockIdx.y) * a.top_k + lane;
+                a.part_d[o] = e.d;
+                a.part_id[o] = e.id;
+            }
         }
     }
 }
@@ -712,6 +763,68 @@ adc_merge(const float* __restrict__ part_d, const long long* __restrict__ part_i
     }
 }
 
+// adc_merge for top_k > 64: the same shares and the same two rounds with the wide list.  A
+// 64-entry piece of the partial lists is one sorted run only when no list ends inside it, that
+// is when top_k is a multiple of 64.
+__global__ void __launch_bounds__(64 * kMergeWaves)
+adc_merge_wide(const float* __restrict__ part_d, const long long* __restrict__ part_id,
+               long long lists, int top_k, long long id_base, float* __restrict__ dist,
+               long long* __restrict__ ids) {
+    __shared__ float xd[(kMergeWaves - 1) * kWideKR * 64];
+    __shared__ long long xid[(kMergeWaves - 1) * kWideKR * 64];
+    const int lane = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    const long long q = blockIdx.x;
+    const long long total = lists * top_k;
+    const int kth = top_k - 1;
+    const bool runs = (top_k & 63) == 0;
+    TopKW e;
+    list_clear(e);
+#pragma unroll 1
+    for (long long base = (long long)wave * 64 * kMergeAhead; base < total;
+         base += 64 * kMergeAhead * kMergeWaves) {
+        float d[kMergeAhead];
+        long long id[kMergeAhead];
+#pragma unroll
+        for (int u = 0; u < kMergeAhead; ++u) {
+            const long long idx = base + u * 64 + lane;
+            d[u] = idx < total ? part_d[q * total + idx] : INFINITY;
+            id[u] = idx < total ? part_id[q * total + idx] : -1ll;
+        }
+#pragma unroll
+        for (int u = 0; u < kMergeAhead; ++u) {
+            if (runs)
+                list_offer<true>(e, d[u], id[u], id[u] >= 0, kth);
+            else
+                list_offer<false>(e, d[u], id[u], id[u] >= 0, kth);
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int b = 0; b < kWideKR; ++b) {
+            xd[((wave - 1) * kWideKR + b) * 64 + lane] = e.d[b];
+            xid[((wave - 1) * kWideKR + b) * 64 + lane] = e.id[b];
+        }
+    }
+    lds_barrier();
+    if (wave == 0) {
+#pragma unroll 1
+        for (int s = 0; s < kMergeWaves - 1; ++s) {
+#pragma unroll 1
+            for (int b = 0; b <= (kth >> 6); ++b) {
+                const long long id = xid[(s * kWideKR + b) * 64 + lane];
+                list_offer<true>(e, xd[(s * kWideKR + b) * 64 + lane], id, id >= 0, kth);
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kWideKR; ++b) {
+            if (b * 64 + lane < top_k) {
+                dist[q * top_k + b * 64 + lane] = e.d[b];
+                ids[q * top_k + b * 64 + lane] = e.id[b] < 0 ? -1ll : e.id[b] + id_base;
+            }
+        }
+    }
+}
 // ------------------------------------------------------------------- host side
 template <int N>
 using Int = std::integral_constant<int, N>;
@@ -724,8 +837,9 @@ int floor_pow2(long long v) {
 
 int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long long lists,
                  long long nq, int top_k, long long id_base, float* d_dist, long long* d_ids) {
-    hipLaunchKernelGGL(adc_merge, dim3((unsigned)nq), dim3(64, kMergeWaves), 0, ctx->stream, pd,
-                       pid, lists, top_k, id_base, d_dist, d_ids);
+    hipLaunchKernelGGL(top_k > PQH_SEARCH_MAX_K ? adc_merge_wide : adc_merge, dim3((unsigned)nq),
+                       dim3(64, kMergeWaves), 0, ctx->stream, pd, pid, lists, top_k, id_base,
+                       d_dist, d_ids);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
 }
@@ -753,7 +867,10 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
     const int m = a.m, k = a.k;
     // the batch's tables: at most 64 KB; 16-part rows keep to four queries (eight running
     // sums beside sixteen unrolled parts spill registers)
-    const int qb = rg ? 1 : (m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
+    // top_k > 64, the wide list: four queries at the most (its entries are registers) and
+    // kWideWavesMax waves (the lists' exchange at the end has to fit the LDS)
+    const bool wide = a.top_k > PQH_SEARCH_MAX_K;
+    const int qb = rg ? 1 : (!wide && m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
     const long long lut_bytes = (long long)m * k * qb * 4;
     const long long budget = kLdsBytes - lut_bytes;
     const long long chunks = (a.n + a.C - 1) / a.C;
@@ -779,7 +896,7 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
     const long long wave_table = rt ? range_table_bytes(m * k) : 0;
     if (per_wave + wave_table > kLdsBytes) return PQH_ERR_UNSUPPORTED;   // (rounding, at most)
     int fit = floor_pow2(std::min<long long>(
-        kScanWavesMax, rt ? kLdsBytes / (per_wave + wave_table) : budget / per_wave));
+        wide ? kWideWavesMax : kScanWavesMax, rt ? kLdsBytes / (per_wave + wave_table) : budget / per_wave));
     a.steps = (chunks + a.L - 1) / a.L;
     // ls: the units are device data, at most one per pair and at most one part-filled per list
     const long long npairs = ls ? a.nq * ls->nprobe : 0;
@@ -873,17 +990,24 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
     const size_t lds = std::max<size_t>(
         rt ? (size_t)waves * (size_t)(wave_table + per_wave)
            : (size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
-        (size_t)waves * qb * 64 * 12);
+        (size_t)waves * qb * (wide ? kWideKR : 1) * 64 * 12);
     auto launch_fl = [&](auto s, auto w, auto c, auto q, auto tb, auto lm, auto fl) -> int {
-        auto* fn = adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
-                            decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value,
-                            decltype(lm)::value, decltype(fl)::value>;
-        if (lds > 64 * 1024)
-            PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(fn, dim3((unsigned)batches, (unsigned)groups), dim3(64, waves), lds,
-                           ctx->stream, a);
-        return PQH_OK;
+        auto go = [&](auto* fn) -> int {
+            if (lds > 64 * 1024)
+                PQH_HIP(ctx, hipFuncSetAttribute((const void*)fn,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(fn, dim3((unsigned)batches, (unsigned)groups), dim3(64, waves), lds,
+                               ctx->stream, a);
+            return PQH_OK;
+        };
+        if constexpr (decltype(q)::value <= 4)
+            if (wide)
+                return go(adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
+                                   decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value,
+                                   decltype(lm)::value, decltype(fl)::value, kWideKR>);
+        return go(adc_scan<decltype(s)::value, decltype(w)::value, decltype(c)::value,
+                           decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value,
+                           decltype(lm)::value, decltype(fl)::value>);
     };
     // a.keep set (the *_masked calls): the filtered form of the same kernel
     auto launch = [&](auto s, auto w, auto c, auto q, auto tb, auto lm) -> int {
@@ -920,7 +1044,7 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
 int search_check(pqh_ctx_t* ctx, bool have_src, long long n, const float* d_lut, long long nq,
                  int top_k, long long id_base, float* d_dist, long long* d_ids, bool* run) {
     *run = false;
-    if (n < 0 || nq < 0 || top_k < 1 || top_k > PQH_SEARCH_MAX_K) return PQH_ERR_ARG;
+    if (n < 0 || nq < 0 || top_k < 1 || top_k > ctx->search_max_k) return PQH_ERR_ARG;
     if (nq > 0 && (!d_lut || !d_dist || !d_ids || (n > 0 && !have_src))) return PQH_ERR_ARG;
     int rc = pqh_use_device(ctx);
     if (rc) return rc;
