@@ -290,7 +290,8 @@ int pqh_decode(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_str
 /* Synchronises; PQH_ERR_CORRUPT if a pqh_decode / pqh_decode_tree / random-access decode
  * (below) on this context since the last call met an invalid code (sticky until read here,
  * like pqh_encode_status); PQH_ERR_ARG if none did but a pqh_decode_select /
- * pqh_fetch_vectors was given a row id outside [0, n). */
+ * pqh_fetch_vectors was given a row id outside [0, n), or a pqh_decode_scatter a destination
+ * outside [-1, n_out). */
 int pqh_decode_status(pqh_ctx_t* ctx);
 
 /* ---- random access through the chunk index (huffman_decoder.c:211-255 and
@@ -670,9 +671,50 @@ int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n], nonzero = 
                   const long long* d_perm /* [n] or NULL */, long long n, unsigned int* d_bits);
 
 /* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe / pqh_ivf_residuals /
- * pqh_mask_pack / pqh_adc_tables_residual on this context since the last call met a bad value (sticky until
+ * pqh_mask_pack / pqh_adc_tables_residual / pqh_ivf_regroup on this context since the last call met a bad value (sticky until
  * read, like pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
+
+/* ---- a mutable inverted file: a list-ordered stream taken to a new list order ------------
+ * The streams hold everything an index is rebuilt from.  pqh_ivf_regroup plans the new order
+ * (rows dropped, gaps left for new rows), pqh_decode_scatter decodes the old stream straight
+ * into it; the new rows' codes are stored into the gaps and the whole is encoded again.
+ * Conventions of the inverted-file calls: device pointers, asynchronous on the context's
+ * stream, a NULL context answered first (PQH_ERR_NO_DEVICE or PQH_ERR_ARG). */
+/* With kept(l) = the rows r of [d_offsets[l], d_offsets[l + 1]) whose bit of d_keep is set
+ * (pqh_mask_pack's format; NULL: all of them) and add(l) = d_add_offsets[l + 1] -
+ * d_add_offsets[l] (NULL: 0):
+ *   d_new_offsets[0] = 0, d_new_offsets[l + 1] = d_new_offsets[l] + kept(l) + add(l)
+ *   d_dest[r] = d_new_offsets[l] + (kept rows of list l before r), or -1 for a dropped row
+ *   d_add_base[l] = d_new_offsets[l] + kept(l)                       (NULL: not wanted)
+ * so within a list the kept old rows keep their order and come first, the gap for the added
+ * rows behind them.  d_offsets int64 [nlist + 1] must cover the stream (d_offsets[0] == 0,
+ * d_offsets[nlist] == n, never decreasing), d_add_offsets -- pqh_ivf_layout's offsets of the
+ * new batch -- must start at 0 and never decrease; otherwise pqh_ivf_status answers PQH_ERR_ARG
+ * and the outputs hold unspecified values, written in bounds.  Limits are pqh_ivf_layout's
+ * (n < 2^31, nlist <= PQH_IVF_MAX_NLIST, else PQH_ERR_UNSUPPORTED).  n == 0 is valid: with
+ * d_add_offsets it plans a pure insertion (d_keep and d_dest are then not looked at).  Uses the
+ * context's scratch when d_keep is given. */
+int pqh_ivf_regroup(pqh_ctx_t* ctx, const long long* d_offsets /* [nlist + 1] */, long long nlist,
+                    long long n, const unsigned int* d_keep /* [ceil(n / 32)] or NULL = all */,
+                    const long long* d_add_offsets /* [nlist + 1] or NULL = none */,
+                    long long* d_new_offsets /* [nlist + 1] */, long long* d_dest /* [n] */,
+                    long long* d_add_base /* [nlist] or NULL */);
+/* pqh_decode through a row map: row r of the stream is stored at d_out[d_dest[r]] where
+ * d_dest[r] >= 0; rows of d_out that are no row's destination are not written.  Stream, index,
+ * code type and shapes are pqh_decode_select's (tree-mode streams out of scope); a chunk of more
+ * than 96 KB of codes is PQH_ERR_UNSUPPORTED.  What is not wanted is not decoded: a chunk is
+ * walked up to its last row with a destination, one without such a row is neither read nor
+ * walked.  Errors are reported by pqh_decode_status: a destination below -1 or >= n_out writes
+ * nothing and gives PQH_ERR_ARG; an invalid code, a chunk offset or a symbol past the stream
+ * gives PQH_ERR_CORRUPT, which takes precedence, and leaves the rows of that chunk unwritten.
+ * Of two rows with the same destination one wins, unspecified which.  n == 0 launches
+ * nothing. */
+int pqh_decode_scatter(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                       unsigned long long stream_bytes, long long n, int raw_first, int chunk_vectors,
+                       const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
+                       const long long* d_dest /* [n] */, void* d_out /* [n_out][m] codes */,
+                       long long n_out);
 
 /* ---- refinement codes: a second compressed stream and a fused re-rank -------------------
  * A row is stored twice: as the PQ code a of the vector (level 1, the stream the searches

@@ -186,6 +186,9 @@ SIGNATURES = [
     ("pqh_search_codes_lists_masked", I,
      [P, P, LL, I, I, P, LL, P, LL, I, P, I, I, LL, P, P, P]),
     ("pqh_mask_pack", I, [P, P, P, LL, P]),
+    ("pqh_ivf_regroup", I, [P, P, LL, LL, P, P, P, P, P]),
+    # pqh_decode_select's stream and index arguments, then the row map, the output and its rows
+    ("pqh_decode_scatter", I, [P, P, P, ULL, LL, I, I, P, P, P, P, LL]),
     # per level (tables, pq, stream, bytes, raw_first, chunk_vectors, offsets, prev), then n
     ("pqh_refine_stream", I,
      [P, P, P, P, ULL, I, I, P, P, P, P, P, ULL, I, I, P, P, LL, P, P, P, LL, LL, P, I, I, P, P,

@@ -25,11 +25,15 @@ calls on device-resident data:
     refine, pq_residuals a second, finer code of what the first quantizer left over, as a stream
                          of its own, and the fused re-rank of a search's candidates with both
                          (IVF.build(refine_pq=...), IVF.search(refine=64), IVF.fetch(refined=True))
+    ivf_regroup, decode_scatter  a list-ordered stream taken to a new list order, rows dropped
+                         and gaps left for new rows: an index that grows and shrinks
+                         (IVF.add, IVF.compact)
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
 (a sort and gathers of int64 in plain torch; Coarse.layout and Coarse.probe are their libpqh
-forms), IVF's gathers through its permutation, the centroid a residual IVF's fetch adds
+forms), IVF's gathers through its permutation and the indexed stores of IVF.add / IVF.compact
+(the new rows' codes into their gaps, perm, inv and the live flags), the centroid a residual IVF's fetch adds
 back and the subtract of pq_residuals (one torch add or sub_ each, not a hot path).  Device buffers are torch tensors owned by
 the caller.
 """
@@ -621,6 +625,24 @@ def decode_range(ctx: Context, tables: Tables, enc: Encoded, first: int, count: 
     return out
 
 
+def decode_scatter(ctx: Context, tables: Tables, enc: Encoded, dest, out):
+    """decode() through a row map: row r of the stream is stored at out[dest[r]] where
+    dest[r] >= 0 (pqh_decode_scatter).  dest: device int64 (enc.n,), as ivf_regroup makes it;
+    out: contiguous codes (n_out, m), only the rows that are a destination written.  A chunk is
+    walked up to its last row with a destination, one without such a row is not read.  Async;
+    decode_status reports a destination outside [-1, n_out) (PQH_ERR_ARG, nothing written for
+    it) and a corrupt chunk (PQH_ERR_CORRUPT, its rows left unwritten)."""
+    torch = _torch()
+    dt = torch.uint8 if tables.k <= 256 else torch.int16
+    if out.dtype != dt or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != tables.m:
+        raise PqhError(-1, "decode_scatter: out is a contiguous tensor of codes of shape (n_out, m)")
+    if dest.dtype != torch.int64 or not dest.is_contiguous() or dest.numel() != enc.n:
+        raise PqhError(-1, "decode_scatter: dest is a contiguous int64 tensor of shape (n,)")
+    check(lib().pqh_decode_scatter(ctx.ptr, tables.ptr, *_index_args(enc), _ptr(dest), _ptr(out),
+                                   out.shape[0]), "pqh_decode_scatter")
+    return out
+
+
 def fetch(ctx: Context, tables: Tables, pq: PQ, enc: Encoded, ids, out=None):
     """reconstructed float vectors of rows `ids`: out[q] = pq.reconstruct of row ids[q], the
     codes never written to memory (pqh_fetch_vectors).  out: (count, >= m * dsub) float32,
@@ -1025,9 +1047,39 @@ class Coarse:
             pass
 
 
+def ivf_regroup(ctx: Context, offsets, keep=None, add_offsets=None, n: int = None):
+    """(new_offsets, dest, add_base): the plan that takes a list-ordered stream to a new list
+    order (pqh_ivf_regroup).  offsets: device int64 (nlist + 1,) of the stream's n rows; keep:
+    the rows that stay, int32 words as pack_mask makes them (None: all); add_offsets: the
+    layout offsets of a batch of new rows (None: none).  In the new order a list holds its kept
+    rows in their old order, then the gap for its added rows: dest int64 (n,) is the new row of
+    every old one (-1: dropped), new_offsets (nlist + 1,) the new lists, add_base (nlist,) the
+    first row of every gap.  n: the stream's rows, where the caller knows them; None reads
+    offsets[-1] (synchronises).  Async otherwise; ivf_status reports offsets that do not cover
+    [0, n) in ascending order."""
+    torch = _torch()
+    if n is None:
+        n = int(offsets[-1].item())
+    nlist = offsets.numel() - 1
+    for name, t in (("offsets", offsets), ("add_offsets", add_offsets)):
+        if t is not None and (t.dtype != torch.int64 or not t.is_contiguous() or
+                              t.numel() != nlist + 1):
+            raise PqhError(-1, f"ivf_regroup: {name} is a contiguous int64 tensor of nlist + 1 entries")
+    if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
+                             keep.numel() < (n + 31) // 32):
+        raise PqhError(-1, "ivf_regroup: keep is a contiguous int32 tensor of ceil(n / 32) words")
+    dev = offsets.device
+    new_offsets = torch.empty(nlist + 1, dtype=torch.int64, device=dev)
+    dest = torch.empty(n, dtype=torch.int64, device=dev)
+    add_base = torch.empty(nlist, dtype=torch.int64, device=dev)
+    check(lib().pqh_ivf_regroup(ctx.ptr, _ptr(offsets), nlist, n, _ptr(keep), _ptr(add_offsets),
+                                _ptr(new_offsets), _ptr(dest), _ptr(add_base)), "pqh_ivf_regroup")
+    return new_offsets, dest, add_base
+
+
 def ivf_status(ctx: Context) -> None:
     """raises PQH_ERR_ARG if a Coarse.layout / Coarse.probe / Coarse.residuals /
-    adc_tables_residual / pack_mask since the last call met a bad value (a list id outside
+    adc_tables_residual / pack_mask / ivf_regroup since the last call met a bad value (a list id outside
     [0, nlist), a reversed offsets pair, a perm entry outside [0, n)); synchronises
     (pqh_ivf_status)"""
     st = lib().pqh_ivf_status(ctx.ptr)
@@ -1062,8 +1114,15 @@ class IVF:
     (c <= 256 after ctx.set_search_max_k(256)) rows of the scan and returns the k best of them by the distance to the sum of both
     reconstructions (codec.refine); fetch(refined=True) returns that sum.
 
+    add(x) appends rows and compact() drops the removed ones for good; both rebuild the streams
+    from the streams themselves (ivf_regroup, decode_scatter, then histogram, tables and encode
+    again), so the index is at any time what build() of its rows would be.  ids are stable:
+    n_ids counts the ids ever given out, an id is never reused, and after a compact() the
+    dropped ones are unknown to the index (inv holds -1 for them).
+
     Every stage is a call on the context's stream.  search() never waits for the device;
-    build() waits where encode() does, once per stream, for the stream's length."""
+    build(), add() and compact() wait where encode() does, once per stream, for the stream's
+    length."""
 
     table_budget = 256 << 20   # bytes of per-(query, list) tables a residual search holds at once
     # schedule="auto": list-major from nq * nprobe >= list_major_ratio * nlist on.  Measured at
@@ -1076,6 +1135,7 @@ class IVF:
     def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets, residual=False):
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
         self.perm, self.inv, self.offsets = perm, inv, offsets
+        self.n_ids = perm.numel()   # ids ever given out: inv's length; perm's until a compact()
         self.residual = residual
         self.refine_pq = self.refine_tables = self.refine_enc = None   # build(refine_pq=...)
         self.live = None         # remove(): device bool per stream row, allocated on first use
@@ -1126,27 +1186,140 @@ class IVF:
     def remove(self, ids) -> None:
         """take the caller rows `ids` (device int64, each in [0, n)) out of every later search,
         with or without keep=.  Tombstones: a live flag per stream row is cleared, the stream
-        is not rebuilt, so fetch() still returns a removed row and the index does not shrink.
-        Removing a row twice is harmless.  Async."""
+        is not rebuilt, so fetch() still returns a removed row and the index does not shrink
+        (compact() does that).  Removing a row twice is harmless, and so is an id that a
+        compact() has dropped.  Async, but for the pass over such ids on a compacted index."""
         torch = _torch()
         if self.live is None:
             self.live = torch.ones(self.perm.numel(), dtype=torch.bool, device=self.perm.device)
-        self.live[self.inv[ids.reshape(-1)]] = False
+        rows = self.inv[ids.reshape(-1)]
+        if self.perm.numel() != self.n_ids:   # compacted: a dropped id has no row
+            rows = rows[rows >= 0]
+        self.live[rows] = False
         self._live_words = pack_mask(self.ctx, self.live)
+
+    def _stage_batch(self, x):
+        """(perm, offsets, list of every sorted row, codes, level-2 codes or None) of a batch of
+        new rows, the codes in the batch's own list order: the stages of build()"""
+        lists = self.coarse.assign(x)
+        perm, offsets = self.coarse.layout(lists)
+        rows = self.coarse.residuals(x, lists, perm) if self.residual else x[perm]
+        codes = self.pq.assign(rows, ctx=self.ctx)
+        codes2 = None
+        if self.refine_pq is not None:
+            rows.sub_(self.pq.reconstruct(codes))
+            codes2 = self.refine_pq.assign(rows, ctx=self.ctx)
+        return perm, offsets, lists[perm].long(), codes, codes2
+
+    def _recode(self, tables, enc, dest, n_new: int, slots=None, codes=None):
+        """(tables, enc) of the stream `enc` taken through the plan `dest` into n_new rows, with
+        `codes` stored at rows `slots`: decode_scatter, histogram, Tables.build, encode"""
+        torch = _torch()
+        merged = torch.empty((n_new, tables.m), dtype=torch.uint8, device=self.perm.device)
+        decode_scatter(self.ctx, tables, enc, dest, merged)
+        if slots is not None:
+            merged[slots] = codes
+        new_tables = Tables(self.ctx, tables.m, tables.k, tables.context).build(
+            histogram(self.ctx, merged, tables.k, tables.context))
+        new_enc = encode(self.ctx, new_tables, merged, chunk_vectors=enc.chunk_vectors)
+        decode_status(self.ctx)
+        return new_tables, new_enc
+
+    def _rebuild(self, keep, batch, n_new: int):
+        """both streams through one plan (ivf_regroup with the mask `keep` and the batch's
+        offsets); returns what replaces the index's state, which is touched by the caller only"""
+        torch = _torch()
+        n = self.perm.numel()
+        new_offsets, dest, add_base = ivf_regroup(
+            self.ctx, self.offsets, keep, None if batch is None else batch[1], n=n)
+        slots = codes = codes2 = None
+        if batch is not None:
+            b_perm, b_offsets, b_lists, codes, codes2 = batch
+            rank = torch.arange(b_perm.numel(), dtype=torch.int64, device=b_perm.device)
+            slots = add_base[b_lists] + (rank - b_offsets[b_lists])
+        level1 = self._recode(self.tables, self.enc, dest, n_new, slots, codes)
+        level2 = None
+        if self.refine_pq is not None:
+            level2 = self._recode(self.refine_tables, self.refine_enc, dest, n_new, slots, codes2)
+        ivf_status(self.ctx)
+        return new_offsets, dest, slots, level1, level2
+
+    def _commit(self, new_offsets, perm, live, level1, level2):
+        torch = _torch()
+        inv = torch.full((self.n_ids,), -1, dtype=torch.int64, device=perm.device)
+        inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
+        self.tables, self.enc = level1
+        if level2 is not None:
+            self.refine_tables, self.refine_enc = level2
+        self.perm, self.inv, self.offsets = perm, inv, new_offsets
+        self.live = live
+        self._live_words = None if live is None else pack_mask(self.ctx, live)
+
+    def add(self, x) -> int:
+        """append the rows of x (device float32 (n_add, d)); returns the id of the first, the
+        rows get the ids n_ids ... n_ids + n_add - 1.  The index is afterwards what build() of
+        all its rows gives, stream for stream: the new rows go through build()'s stages (rows to
+        lists, layout, residuals, pq.assign, the level-2 codes), the old stream is decoded
+        straight into the merged list order (ivf_regroup, decode_scatter), and histogram, tables
+        and encode run again with the index's own chunk_vectors and context.  So the cost is
+        O(n + n_add) per call, everything is re-coded: add in large batches.  Rows taken out by
+        remove() stay stored and stay out; add() drops nothing.  Waits where encode() does, once
+        per stream.  A PqhError leaves the index as it was.  n_add == 0 does nothing."""
+        torch = _torch()
+        n_add = x.shape[0]
+        first = self.n_ids
+        if n_add == 0:
+            return first
+        if x.dim() != 2 or x.shape[1] != self.coarse.d:
+            raise PqhError(-1, "IVF.add: x, the coarse centroids and the PQ disagree in d")
+        n = self.perm.numel()
+        batch = self._stage_batch(x)
+        new_offsets, dest, slots, level1, level2 = self._rebuild(None, batch, n + n_add)
+        perm = torch.empty(n + n_add, dtype=torch.int64, device=self.perm.device)
+        perm[dest] = self.perm
+        perm[slots] = batch[0] + first
+        live = None
+        if self.live is not None:
+            live = torch.ones(n + n_add, dtype=torch.bool, device=self.perm.device)
+            live[dest] = self.live
+        self.n_ids = first + n_add
+        self._commit(new_offsets, perm, live, level1, level2)
+        return first
+
+    def compact(self) -> int:
+        """drop the rows remove() took out for good; returns how many.  The streams, perm and
+        offsets shrink to the live rows -- the same pass as add(), with the live words as the
+        mask and no new rows, so the cost is O(n) -- and the live flags are reset.  ids stay
+        what they were: perm holds the caller's ids, inv keeps n_ids entries with -1 for the
+        dropped ones, which remove() then ignores, fetch() reports (see there) and keep= still
+        has an entry for.  Without a removed row nothing is touched.  Waits where encode() does,
+        once per stream, and once for the count.  A PqhError leaves the index as it was."""
+        if self.live is None:
+            return 0
+        n = self.perm.numel()
+        n_live = int(self.live.sum().item())
+        if n_live == n:
+            return 0
+        new_offsets, _, _, level1, level2 = self._rebuild(self._live_words, None, n_live)
+        self._commit(new_offsets, self.perm[self.live], None, level1, level2)
+        return n - n_live
 
     def live_count(self) -> int:
         """the rows remove() has left (synchronises once a row was removed)"""
         return self.perm.numel() if self.live is None else int(self.live.sum().item())
 
     def _mask(self, keep):
-        """the words of keep (bool over the caller's rows, packed through perm into stream
-        order) ANDed with those of the live rows; None: no filter"""
+        """the words of keep (bool over the ids, packed through perm into stream order) ANDed
+        with those of the live rows; None: no filter"""
         torch = _torch()
         if keep is None:
             return self._live_words
-        if keep.dtype != torch.bool or keep.shape != (self.perm.numel(),):
-            raise PqhError(-1, "IVF.search: keep is a bool tensor of shape (n,)")
-        words = pack_mask(self.ctx, keep, self.perm)
+        if keep.dtype != torch.bool or keep.shape != (self.n_ids,):
+            raise PqhError(-1, "IVF.search: keep is a bool tensor of shape (n_ids,)")
+        if self.perm.numel() == self.n_ids:
+            words = pack_mask(self.ctx, keep, self.perm)
+        else:   # compacted: fewer rows than ids, so the gather comes first
+            words = pack_mask(self.ctx, keep[self.perm])
         return words if self._live_words is None else words & self._live_words
 
     def search(self, queries, nprobe: int, k: int, schedule: str = "query", keep=None,
@@ -1156,7 +1329,7 @@ class IVF:
         schedule: "query" decodes a list once for every query that probes it (search_ranges),
         "list" once per batch of the queries that probe it (search_lists), "auto" takes "list"
         from nq * nprobe >= list_major_ratio * nlist on; the result is the same bits.
-        keep: device bool (n,) over the caller's rows of x: only rows with keep[id] set are
+        keep: device bool (n_ids,) over the ids (the caller's rows of x): only rows with keep[id] set are
         returned -- the k nearest among them, not the kept ones of the k nearest.  Rows taken
         out by remove() are never returned.
         refine: 0, or the number c of candidates, k <= c <= ctx.search_max_k, on an index built
@@ -1241,7 +1414,9 @@ class IVF:
         residual plus the centroid of the stream row's list, one fp32 add).  refined=True, on an
         index built with refine_pq: the level-2 reconstruction is fetched too and added first,
         (c1 + c2) and then + centroid -- the vectors search(refine=...) measures against.
-        remove() does not affect it: the stream still holds a removed row."""
+        remove() does not affect it: the stream still holds a removed row.  After a compact()
+        it does not: the row of a dropped id comes back as zeros (residual: the first list's
+        centroid) and decode_status reports PQH_ERR_ARG, as for any id the index does not know."""
         torch = _torch()
         if refined and self.refine_pq is None:
             raise PqhError(-1, "IVF.fetch: refined=True on an index built without refine_pq")

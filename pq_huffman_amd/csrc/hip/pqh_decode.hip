@@ -443,33 +443,6 @@ int sel_check(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stre
     return pqh_use_device(ctx);
 }
 
-// A packed row: 8 or 16 bytes of u8 codes, or 8 u16 codes, with the chunk contexts readable
-// as u64 words.  Returns its u64 words (1 or 2), or 0 for the per-part kernels.
-int packed_row_words(const pqh_tables_t* t, const void* d_chunk_prev) {
-    const int esz = t->k <= 256 ? 1 : 2;
-    const int row_bytes = t->m * esz;
-    const bool packed = (row_bytes == 8 || row_bytes == 16) && (esz == 1 || t->m == 8) &&
-                        !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
-    return packed ? row_bytes / 8 : 0;
-}
-
-// f(CodeT(), NW, CTX) with the table set's code type, the row's u64 words nw (0: per part)
-// and the context flag as compile-time values (u16 codes are never context coded)
-template <int N>
-using Int = std::integral_constant<int, N>;
-template <typename F>
-int with_shape(const pqh_tables_t* t, int nw, F&& f) {
-    if (t->k > 256)
-        return nw ? f(uint16_t(), Int<2>(), std::false_type())
-                  : f(uint16_t(), Int<0>(), std::false_type());
-    auto with_nw = [&](auto ctx) -> int {
-        return nw == 1   ? f(uint8_t(), Int<1>(), ctx)
-               : nw == 2 ? f(uint8_t(), Int<2>(), ctx)
-                         : f(uint8_t(), Int<0>(), ctx);
-    };
-    return t->context ? with_nw(std::true_type()) : with_nw(std::false_type());
-}
-
 // sel_rows over `count` ids: codes [count][m] (FETCH = false) or float rows ld_out apart
 template <bool FETCH>
 int sel_launch(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
