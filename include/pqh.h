@@ -569,6 +569,79 @@ int pqh_search_codes_lists_masked(pqh_ctx_t* ctx, const void* d_codes, long long
                                   long long id_base, float* d_dist, long long* d_ids,
                                   const unsigned int* d_keep);
 
+/* Range search: every scanned row v with dist(q, v) < d_radius[q] (strict), as many as there
+ * are -- what no fixed top_k can give.  dist is the searches' own fp32 sum, ((lut[0][c_0] +
+ * lut[1][c_1]) + ...) without contraction.  A NaN radius or a NaN distance gives no hit;
+ * radius = +inf gives every row whose distance is below +inf.
+ * The rows scanned are those of the searches above, by the probe list:
+ *   d_range_ptr == NULL, d_ranges == NULL, nr == -1, tables_per_range == 0: the whole stream,
+ *     d_lut [nq][m][K] (pqh_search_stream / pqh_search_codes);
+ *   else query q's ranges d_ranges[r] = (first row, count), r in [d_range_ptr[q],
+ *     d_range_ptr[q + 1]), with d_lut [nq][m][K] (tables_per_range == 0, pqh_search_*_ranges) or
+ *     one table per range, d_lut [nr][m][K] (tables_per_range != 0, pqh_search_*_range_tables).
+ * d_keep: the row mask of the _masked calls ([ceil(n / 32)] words, only kept rows are hits and
+ * what is not kept is not decoded) or NULL.
+ * The result is CSR: d_lims [nq + 1] (int64, d_lims[0] = 0), and d_dist / d_ids entries
+ * [d_lims[q], d_lims[q + 1]) for query q, ids = stream rows + id_base, in scan order: ascending
+ * stream row for the whole stream; in the probe forms range by range in the order of the
+ * query's list, ascending row inside a range, and a row under two overlapping or repeated
+ * ranges once per range.  Bits and order do not depend on the grid or on
+ * PQH_TUNE_SEARCH_GROUPS.
+ * Two passes over a plan in the CALLER's device memory (8-byte aligned, at least
+ * pqh_range_plan_bytes bytes: a header, 8 bytes per query, workgroup and wave of the scan, and
+ * 8 per batch of queries, workgroup and wave):
+ *   pqh_range_count_*  scans, counts every wave's hits per query into the plan, turns the counts
+ *                      into offsets and writes d_lims.  The header records the launch geometry.
+ *   pqh_range_fill_*   takes the same arguments, the plan and d_lims as the count left them, and
+ *                      scans again: every wave writes its hits from its offset on.  Entry p is
+ *                      written only if p < capacity, so a buffer that is too small holds the
+ *                      first `capacity` entries of the full result and nothing past it is
+ *                      touched; d_lims always holds the full counts, and truncation is no error
+ *                      (compare d_lims[nq] with capacity).  A wave whose share of the scan
+ *                      counted no hit decodes nothing, and one that has written all it counted
+ *                      stops.  The fill may be repeated.
+ * Nothing on the context has to survive between the two calls.  A fill whose own geometry is
+ * not the plan's (the tuning changed in between, another n or nq) writes nothing and sets the
+ * sticky bit that pqh_decode_status reports as PQH_ERR_ARG.
+ * Async.  The checks, limits (K <= 256, m <= 16, else PQH_ERR_UNSUPPORTED) and errors are the
+ * searches': a NULL context is answered first; a chunk offset or symbol past the stream or an
+ * invalid code gives PQH_ERR_CORRUPT from pqh_decode_status and the rows of that chunk are no
+ * hits; a bad range or d_range_ptr entry gives PQH_ERR_ARG there and no steps; plan_bytes below
+ * pqh_range_plan_bytes is PQH_ERR_ARG.  nq == 0, n == 0 and nr == 0 launch at most the write of
+ * d_lims (all zero).
+ * pqh_range_plan_bytes: chunk_vectors = 0 for the *_codes calls. */
+int pqh_range_plan_bytes(pqh_ctx_t* ctx, long long n, int m, int k, int chunk_vectors,
+                         long long nq, long long nr /* -1: the whole stream */,
+                         int tables_per_range, unsigned long long* bytes);
+int pqh_range_count_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                           unsigned long long stream_bytes, long long n, int raw_first,
+                           int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                           const void* d_chunk_prev, const float* d_lut, long long nq,
+                           const long long* d_range_ptr, const long long* d_ranges, long long nr,
+                           int tables_per_range, const float* d_radius /* [nq] */,
+                           const unsigned int* d_keep /* [ceil(n / 32)] or NULL */, void* d_plan,
+                           unsigned long long plan_bytes, long long* d_lims /* [nq + 1] */);
+int pqh_range_fill_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
+                          unsigned long long stream_bytes, long long n, int raw_first,
+                          int chunk_vectors, const unsigned long long* d_chunk_offsets,
+                          const void* d_chunk_prev, const float* d_lut, long long nq,
+                          const long long* d_range_ptr, const long long* d_ranges, long long nr,
+                          int tables_per_range, const float* d_radius, const unsigned int* d_keep,
+                          const void* d_plan, unsigned long long plan_bytes,
+                          const long long* d_lims, long long capacity, long long id_base,
+                          float* d_dist /* [capacity] */, long long* d_ids /* [capacity] */);
+int pqh_range_count_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                          const float* d_lut, long long nq, const long long* d_range_ptr,
+                          const long long* d_ranges, long long nr, int tables_per_range,
+                          const float* d_radius, const unsigned int* d_keep, void* d_plan,
+                          unsigned long long plan_bytes, long long* d_lims);
+int pqh_range_fill_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
+                         const float* d_lut, long long nq, const long long* d_range_ptr,
+                         const long long* d_ranges, long long nr, int tables_per_range,
+                         const float* d_radius, const unsigned int* d_keep, const void* d_plan,
+                         unsigned long long plan_bytes, const long long* d_lims,
+                         long long capacity, long long id_base, float* d_dist, long long* d_ids);
+
 /* ---- inverted file: coarse quantizer, list layout, probe selection ---------------------
  * The front end of the probe search: rows are assigned to the nearest of nlist coarse
  * centroids (full d-dimensional vectors), stored list by list, and a query probes the nprobe

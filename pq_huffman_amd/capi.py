@@ -186,6 +186,16 @@ SIGNATURES = [
     ("pqh_search_codes_lists_masked", I,
      [P, P, LL, I, I, P, LL, P, LL, I, P, I, I, LL, P, P, P]),
     ("pqh_mask_pack", I, [P, P, P, LL, P]),
+    # range search: the source, the tables, the probe list (NULL, NULL, -1, 0: the whole stream),
+    # radius, keep, plan, plan bytes, lims -- and for the fill capacity, id_base, dist, ids
+    ("pqh_range_plan_bytes", I, [P, LL, I, I, I, LL, LL, I, P]),
+    ("pqh_range_count_stream", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, P, P, P, ULL, P]),
+    ("pqh_range_fill_stream", I,
+     [P, P, P, ULL, LL, I, I, P, P, P, LL, P, P, LL, I, P, P, P, ULL, P, LL, LL, P, P]),
+    ("pqh_range_count_codes", I, [P, P, LL, I, I, P, LL, P, P, LL, I, P, P, P, ULL, P]),
+    ("pqh_range_fill_codes", I,
+     [P, P, LL, I, I, P, LL, P, P, LL, I, P, P, P, ULL, P, LL, LL, P, P]),
     ("pqh_ivf_regroup", I, [P, P, LL, LL, P, P, P, P, P]),
     # pqh_decode_select's stream and index arguments, then the row map, the output and its rows
     ("pqh_decode_scatter", I, [P, P, P, ULL, LL, I, I, P, P, P, P, LL]),

@@ -923,6 +923,99 @@ def search_codes_lists(ctx: Context, codes, lut, offsets, probes, k: int, id_bas
     return dist, ids
 
 
+def _range_search(ctx: Context, name: str, src, n: int, m: int, k: int, chunk_vectors: int, lut,
+                  nq: int, probe, radius, keep, id_base: int, capacity):
+    """count, (read the total,) fill: pqh_range_count_<name> and pqh_range_fill_<name> over a
+    plan allocated here.  src: the calls' leading arguments; probe: None (the whole stream) or
+    (range_ptr, ranges, tables_per_range)."""
+    torch = _torch()
+    dev = lut.device
+    if torch.is_tensor(radius):
+        if radius.dtype != torch.float32 or radius.shape != (nq,):
+            raise PqhError(-1, f"range_search: radius is a float or a float32 tensor of shape ({nq},)")
+        radius = radius.contiguous()
+    else:
+        radius = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+    if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
+                             keep.numel() < (n + 31) // 32):
+        raise PqhError(-1, "range_search: keep is a contiguous int32 tensor of ceil(n / 32) words")
+    if probe is None:
+        list_args = (None, None, -1, 0)
+    else:
+        range_ptr, ranges, per_range = probe
+        list_args = (_ptr(range_ptr), _ptr(ranges), ranges.shape[0], int(bool(per_range)))
+    nbytes = ctypes.c_ulonglong(0)
+    check(lib().pqh_range_plan_bytes(ctx.ptr, n, m, k, chunk_vectors, nq, list_args[2],
+                                     list_args[3], ctypes.byref(nbytes)), "pqh_range_plan_bytes")
+    plan = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
+    lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    args = (ctx.ptr, *src, _ptr(lut), nq, *list_args, _ptr(radius), _ptr(keep), _ptr(plan),
+            plan.numel() * 8, _ptr(lims))
+    check(getattr(lib(), f"pqh_range_count_{name}")(*args), f"pqh_range_count_{name}")
+    if capacity is None:
+        capacity = int(lims[-1].item())     # the one synchronisation
+        dist = torch.empty(capacity, dtype=torch.float32, device=dev)
+        ids = torch.empty(capacity, dtype=torch.int64, device=dev)
+    else:
+        dist = torch.full((capacity,), float("inf"), dtype=torch.float32, device=dev)
+        ids = torch.full((capacity,), -1, dtype=torch.int64, device=dev)
+    check(getattr(lib(), f"pqh_range_fill_{name}")(*args, capacity, id_base, _ptr(dist), _ptr(ids)),
+          f"pqh_range_fill_{name}")
+    return lims, dist, ids
+
+
+def range_search(ctx: Context, tables: Tables, enc: Encoded, lut, radius, keep=None,
+                 id_base: int = 0, capacity=None):
+    """(lims, dist, ids): every row of the stream with dist < radius[q] (strict; search()'s
+    fp32 sum), as many as there are, in CSR form: query q's hits are dist / ids
+    [lims[q], lims[q + 1]) in ascending stream row, ids = stream rows + id_base; lims int64
+    (nq + 1,), dist float32 and ids int64 (lims[nq],).  Two scans of the stream
+    (pqh_range_count_stream, pqh_range_fill_stream): the first counts, the second writes, and
+    where the first counted nothing the second decodes nothing.  A NaN radius or distance is no
+    hit; bits and order do not depend on the grid.
+    radius: a float, or a device float32 tensor (nq,).  keep: the row mask of search().
+    capacity=None: the outputs are allocated exactly, which waits once for the device to read
+    lims[-1] between the two scans (as encode() does for the stream's length).  capacity=int:
+    no wait; dist and ids have that length, hold the first `capacity` entries of the result and
+    (+inf, -1) behind lims[-1]; lims always holds the full counts, so lims[-1] > capacity says
+    that the result was cut.  Async otherwise; decode_status reports a corrupt stream."""
+    return _range_search(ctx, "stream", (tables.ptr, *_index_args(enc)), enc.n, tables.m, tables.k,
+                         enc.chunk_vectors, lut, lut.shape[0], None, radius, keep, id_base, capacity)
+
+
+def range_search_codes(ctx: Context, codes, lut, radius, keep=None, id_base: int = 0,
+                       capacity=None):
+    """range_search() over plain uint8 codes (n, m) (pqh_range_count_codes, pqh_range_fill_codes)."""
+    n, m = codes.shape
+    return _range_search(ctx, "codes", (_ptr(codes), n, m, lut.shape[2]), n, m, lut.shape[2], 0,
+                         lut, lut.shape[0], None, radius, keep, id_base, capacity)
+
+
+def range_search_ranges(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ranges, radius,
+                        tables_per_range: bool = False, keep=None, id_base: int = 0,
+                        capacity=None):
+    """range_search() of per-query row ranges (search_ranges' probe list; tables_per_range:
+    lut (nr, m, K), range r scored with lut[r], as search_range_tables).  Query q's hits come
+    range by range in the order of its list, ascending row inside a range; a row under two
+    overlapping or repeated ranges appears once per range.  decode_status also reports a bad
+    range or range_ptr value (PQH_ERR_ARG, the range or query skipped)."""
+    nq = range_ptr.numel() - 1
+    return _range_search(ctx, "stream", (tables.ptr, *_index_args(enc)), enc.n, tables.m, tables.k,
+                         enc.chunk_vectors, lut, nq, (range_ptr, ranges, tables_per_range), radius,
+                         keep, id_base, capacity)
+
+
+def range_search_codes_ranges(ctx: Context, codes, lut, range_ptr, ranges, radius,
+                              tables_per_range: bool = False, keep=None, id_base: int = 0,
+                              capacity=None):
+    """range_search_ranges() over plain uint8 codes (n, m)."""
+    n, m = codes.shape
+    nq = range_ptr.numel() - 1
+    return _range_search(ctx, "codes", (_ptr(codes), n, m, lut.shape[2]), n, m, lut.shape[2], 0,
+                         lut, nq, (range_ptr, ranges, tables_per_range), radius, keep, id_base,
+                         capacity)
+
+
 def ivf_layout(list_ids, nlist: int):
     """(perm, offsets) for storing rows list by list: perm is the stable order of the rows by
     list id (stream row s holds original row perm[s]), offsets int64 (nlist + 1,) with list l
@@ -1120,9 +1213,13 @@ class IVF:
     n_ids counts the ids ever given out, an id is never reused, and after a compact() the
     dropped ones are unknown to the index (inv holds -1 for them).
 
+    range_search(queries, nprobe, radius) returns every row of the probed lists closer than
+    radius, as many as there are (CSR: lims, dist, ids), where search() returns the k nearest.
+
     Every stage is a call on the context's stream.  search() never waits for the device;
-    build(), add() and compact() wait where encode() does, once per stream, for the stream's
-    length."""
+    range_search() waits once per slab of queries (once on a plain index), for the number of
+    hits it has to allocate; build(), add() and compact() wait where encode() does, once per
+    stream, for the stream's length."""
 
     table_budget = 256 << 20   # bytes of per-(query, list) tables a residual search holds at once
     # schedule="auto": list-major from nq * nprobe >= list_major_ratio * nlist on.  Measured at
@@ -1407,6 +1504,50 @@ class IVF:
             if refine_k:
                 self._refine(q, out[1], refine_k, out=(fine[0][s:s + slab], fine[1][s:s + slab]))
         return fine if refine_k else (dist, rows)
+
+    def range_search(self, queries, nprobe: int, radius, keep=None):
+        """(lims, dist, ids): every row of each query's nprobe nearest lists with an ADC distance
+        below radius (codec.range_search_ranges: strict, CSR, as many hits as there are); ids are
+        rows of the caller's x, a query's hits list by list in the order of its probes, in
+        stream order inside a list.  radius: a float, or a device float32 tensor (nq,).  keep
+        and remove() act as in search().  A residual index scores every (query, list) pair with
+        its own table, slab by slab under table_budget, and the slabs' results are concatenated.
+        Unlike search(), it waits for the device: once per slab (once for a plain index), for
+        the number of hits."""
+        torch = _torch()
+        nq = queries.shape[0]
+        mask = self._mask(keep)
+        if torch.is_tensor(radius):
+            if radius.dtype != torch.float32 or radius.shape != (nq,):
+                raise PqhError(-1, "IVF.range_search: radius is a float or a float32 tensor (nq,)")
+        else:
+            radius = torch.full((nq,), float(radius), dtype=torch.float32, device=queries.device)
+        if not self.residual:
+            lut = adc_tables(self.ctx, self.pq, queries)
+            range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False)
+            lims, dist, rows = range_search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr,
+                                                   ranges, radius, keep=mask)
+            return lims, dist, self.perm[rows]
+        per_query = nprobe * self.pq.m * self.pq.k * 4
+        slab = max(1, min(max(nq, 1), int(self.table_budget) // per_query))
+        lut = torch.empty((slab * nprobe, self.pq.m, self.pq.k), dtype=torch.float32,
+                          device=queries.device)
+        lims = torch.zeros(nq + 1, dtype=torch.int64, device=queries.device)
+        parts = []
+        for s in range(0, nq, slab):
+            q = queries[s:s + slab]
+            range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True)
+            adc_tables_residual(self.ctx, self.pq, self.coarse, q, probes,
+                                out=lut[:q.shape[0] * nprobe])
+            l, d, r = range_search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges,
+                                          radius[s:s + slab], tables_per_range=True, keep=mask)
+            lims[s + 1:s + 1 + q.shape[0]] = l[1:] + lims[s]
+            parts.append((d, r))
+        if not parts:
+            return (lims, torch.empty(0, dtype=torch.float32, device=queries.device),
+                    torch.empty(0, dtype=torch.int64, device=queries.device))
+        dist = torch.cat([p[0] for p in parts])
+        return lims, dist, self.perm[torch.cat([p[1] for p in parts])]
 
     def fetch(self, ids, out=None, refined: bool = False):
         """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)): what
