@@ -744,8 +744,9 @@ int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n], nonzero = 
                   const long long* d_perm /* [n] or NULL */, long long n, unsigned int* d_bits);
 
 /* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe / pqh_ivf_residuals /
- * pqh_mask_pack / pqh_adc_tables_residual / pqh_ivf_regroup on this context since the last call met a bad value (sticky until
- * read, like pqh_decode_status). */
+ * pqh_mask_pack / pqh_adc_tables_residual / pqh_ivf_regroup / pqh_idmap_* / pqh_mask_pack_idmap
+ * on this context since the last call met a bad value (sticky until read, like
+ * pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
 
 /* ---- a mutable inverted file: a list-ordered stream taken to a new list order ------------
@@ -788,6 +789,74 @@ int pqh_decode_scatter(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned cha
                        const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
                        const long long* d_dest /* [n] */, void* d_out /* [n_out][m] codes */,
                        long long n_out);
+
+/* ---- compressed ids: an Elias-Fano id map for the inverted file --------------------------
+ * pqh_ivf_layout's d_perm is a stable order by list, pqh_ivf_regroup keeps a list's old rows in
+ * their order in front of the new ones, and new rows get ids above every old one: within a list
+ * the ids ascend strictly, so with B = the bit width of n_ids - 1
+ *   key(s) = (list(s) << B) | d_perm[s]
+ * ascends strictly over the stream.  The map stores the n keys below nlist << B in Elias-Fano
+ * form -- about 2 + log2(nlist) bits a row, with random access -- as one device blob of 64-bit
+ * words (8-byte aligned, else PQH_ERR_ARG), L = max(0, floor(log2((nlist << B) / n))):
+ *   header   16 words: a magic word, n, n_ids, nlist, B, L, the word offset of the low bits,
+ *            that of the high bits and their words, that of the samples and their count, that
+ *            of the reverse part and the bytes of one of its entries (0: no reverse part), the
+ *            words of the blob, two words of zeros
+ *   low      n fields of L bits (L <= 55), field s at bit s * L counted from bit 0 of word 0 of
+ *            the part: a field may straddle two words; L == 0: no words
+ *   high     bit (key(s) >> L) + s is set for every row s, ((nlist << B) - 1 >> L) + n bits
+ *            (fewer than 3 n + 1)
+ *   samples  one word per 256 rows: (key(256 j) >> L) + 256 j, the high-bit position of row 256 j
+ *   reverse  (optional) the list of every id of [0, n_ids): u16 where nlist <= 65535, 0xFFFF =
+ *            the id has no row; int32 otherwise, -1 = no row; padded to a word
+ * Every part is padded to whole words and every bit that no field owns is zero, so two maps of
+ * the same (d_perm, d_offsets, n_ids, nlist) are equal byte for byte.  n == 0 is a valid map: the
+ * header (and the reverse part, all "no row").
+ * Conventions of the inverted-file calls: device pointers, asynchronous on the context's stream,
+ * a NULL context answered first, bad device data reported by pqh_ivf_status (sticky PQH_ERR_ARG)
+ * with nothing read or written out of bounds; count == 0 launches nothing.  d_map of every call
+ * but pqh_idmap_build is a blob that call wrote. */
+/* The bytes of the blob: host arithmetic only, no GPU.  0 <= n <= n_ids and nlist >= 1, else
+ * PQH_ERR_ARG; n_ids < 2^31 and nlist <= PQH_IVF_MAX_NLIST, else PQH_ERR_UNSUPPORTED.  Without
+ * the reverse part the blob is at most n * (L + 3) / 8 + n / 32 + 4096 bytes. */
+int pqh_idmap_bytes(long long n, long long n_ids, long long nlist, int reverse,
+                    unsigned long long* bytes);
+/* Writes the blob of d_perm int64 [n] and d_offsets int64 [nlist + 1] as pqh_ivf_layout gives
+ * them (after pqh_ivf_regroup: the new order's).  map_bytes below pqh_idmap_bytes is
+ * PQH_ERR_CAPACITY.  Checks what it codes: a d_perm entry outside [0, n_ids), a row outside the
+ * list d_offsets puts it in, or two neighbouring rows whose keys do not ascend (two equal ids,
+ * a descending pair in a list) make pqh_ivf_status answer PQH_ERR_ARG; the map is then
+ * unspecified, but every later call on it stays in bounds.  Two memsets and one launch (n == 0:
+ * the launch writes the header). */
+int pqh_idmap_build(pqh_ctx_t* ctx, const long long* d_perm /* [n] */,
+                    const long long* d_offsets /* [nlist + 1] */, long long n, long long nlist,
+                    long long n_ids, int reverse, void* d_map, unsigned long long map_bytes);
+/* d_ids[i] = the id of stream row d_rows[i], one lane per row, rows in any order and repeated
+ * at will.  A row < 0 is copied through (the -1 padding of a search result); a row >= n gives
+ * -1 and PQH_ERR_ARG from pqh_ivf_status. */
+int pqh_idmap_ids(pqh_ctx_t* ctx, const void* d_map, const long long* d_rows /* [count] */,
+                  long long count, long long* d_ids /* [count] */);
+/* The ids of the rows [first, first + count), any first and count: the streaming form, a wave per
+ * block of 256 rows.  A row >= n gives -1 and PQH_ERR_ARG from pqh_ivf_status; first < 0 or
+ * count < 0 is PQH_ERR_ARG at once. */
+int pqh_idmap_decode(pqh_ctx_t* ctx, const void* d_map, long long first, long long count,
+                     long long* d_ids /* [count] */);
+/* d_rows[i] = the stream row of id d_ids[i], or -1 where the id has none (a row dropped from
+ * the index): the id's list from the reverse part, then a binary search over the rows
+ * d_offsets[l] ... d_offsets[l + 1] of that list (cut to [0, n] whatever they hold).  An id
+ * outside [0, n_ids) gives -1 and PQH_ERR_ARG from pqh_ivf_status; so does every id on a map
+ * built without a reverse part (the header lives on the device and the call does not wait for
+ * it: codec.IdMap.rows refuses such a map at once). */
+int pqh_idmap_rows(pqh_ctx_t* ctx, const void* d_map, const long long* d_offsets /* [nlist + 1] */,
+                   const long long* d_ids /* [count] */, long long count,
+                   long long* d_rows /* [count] */);
+/* pqh_mask_pack through the map: bit s & 31 of d_bits[s >> 5] = d_keep[id(s)] != 0 for the n
+ * rows of the map, the words pqh_mask_pack(d_keep, d_perm) writes in every bit below n, the bits
+ * from n on in the last word zeros; d_perm is never materialised.  d_keep u8 [n_ids], d_bits
+ * [ceil(n / 32)] words (4-byte aligned).  n is the map's (the grid is sized by it): another n
+ * writes zeros and gives PQH_ERR_ARG from pqh_ivf_status.  n == 0 launches nothing. */
+int pqh_mask_pack_idmap(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n_ids] */,
+                        const void* d_map, long long n, unsigned int* d_bits);
 
 /* ---- refinement codes: a second compressed stream and a fused re-rank -------------------
  * A row is stored twice: as the PQ code a of the vector (level 1, the stream the searches

@@ -199,6 +199,14 @@ SIGNATURES = [
     ("pqh_ivf_regroup", I, [P, P, LL, LL, P, P, P, P, P]),
     # pqh_decode_select's stream and index arguments, then the row map, the output and its rows
     ("pqh_decode_scatter", I, [P, P, P, ULL, LL, I, I, P, P, P, P, LL]),
+    # the Elias-Fano id map: bytes (host only), build, rows -> ids, a row range, ids -> rows,
+    # and pqh_mask_pack through the map
+    ("pqh_idmap_bytes", I, [LL, LL, LL, I, P]),
+    ("pqh_idmap_build", I, [P, P, P, LL, LL, LL, I, P, ULL]),
+    ("pqh_idmap_ids", I, [P, P, P, LL, P]),
+    ("pqh_idmap_decode", I, [P, P, LL, LL, P]),
+    ("pqh_idmap_rows", I, [P, P, P, P, LL, P]),
+    ("pqh_mask_pack_idmap", I, [P, P, P, LL, P]),
     # per level (tables, pq, stream, bytes, raw_first, chunk_vectors, offsets, prev), then n
     ("pqh_refine_stream", I,
      [P, P, P, P, ULL, I, I, P, P, P, P, P, ULL, I, I, P, P, LL, P, P, P, LL, LL, P, I, I, P, P,

@@ -28,6 +28,9 @@ calls on device-resident data:
     ivf_regroup, decode_scatter  a list-ordered stream taken to a new list order, rows dropped
                          and gaps left for new rows: an index that grows and shrinks
                          (IVF.add, IVF.compact)
+    IdMap, idmap_bytes   an index's ids in Elias-Fano form in place of the int64 perm and inv:
+                         rows to ids, ids to rows, a row range, and pack_mask through the map
+                         (IVF.build(compress_ids=True), IVF.compress_ids)
 
 torch is used only for device memory and the stream (data_ptr / cuda_stream); every
 computation is a libpqh kernel, but for the index bookkeeping of ivf_layout and probe_ranges
@@ -1172,12 +1175,115 @@ def ivf_regroup(ctx: Context, offsets, keep=None, add_offsets=None, n: int = Non
 
 def ivf_status(ctx: Context) -> None:
     """raises PQH_ERR_ARG if a Coarse.layout / Coarse.probe / Coarse.residuals /
-    adc_tables_residual / pack_mask / ivf_regroup since the last call met a bad value (a list id outside
-    [0, nlist), a reversed offsets pair, a perm entry outside [0, n)); synchronises
+    adc_tables_residual / pack_mask / ivf_regroup / IdMap call since the last call met a bad
+    value (a list id outside [0, nlist), a reversed offsets pair, a perm entry outside [0, n), a
+    row or id an IdMap does not hold); synchronises
     (pqh_ivf_status)"""
     st = lib().pqh_ivf_status(ctx.ptr)
     if st:
         raise PqhError(st, "pqh_ivf")
+
+
+def idmap_bytes(n: int, n_ids: int, nlist: int, reverse: bool = True) -> int:
+    """the bytes of the id map of n rows in nlist lists with ids below n_ids (pqh_idmap_bytes;
+    host arithmetic, runs without a GPU)"""
+    out = ctypes.c_ulonglong(0)
+    check(lib().pqh_idmap_bytes(n, n_ids, nlist, int(bool(reverse)), ctypes.byref(out)),
+          "pqh_idmap_bytes")
+    return out.value
+
+
+class IdMap:
+    """The ids of a list-ordered stream in Elias-Fano form (include/pqh.h, "compressed ids"):
+    what an IVF's perm (stream row -> id) and inv (id -> stream row) hold, in about
+    2 + log2(nlist) bits a row plus, with reverse=True, a list number per id.  perm: device
+    int64 (n,), ascending inside every list; offsets: device int64 (nlist + 1,); both as
+    Coarse.layout gives them.  Neither is kept, but for offsets as the default of rows().
+    Async; ivf_status reports a perm the map cannot code (an id outside [0, n_ids), a list
+    whose ids do not ascend).
+
+    blob: the device uint8 tensor of the map; nbytes, n, n_ids, nlist, reverse."""
+
+    def __init__(self, ctx: Context, perm, offsets, n_ids: int, reverse: bool = True):
+        torch = _torch()
+        for name, t in (("perm", perm), ("offsets", offsets)):
+            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+                raise PqhError(-1, f"IdMap: {name} is a contiguous int64 vector")
+        self.ctx, self.offsets = ctx, offsets
+        self.n, self.n_ids, self.nlist = perm.numel(), int(n_ids), offsets.numel() - 1
+        self.reverse = bool(reverse)
+        self.nbytes = idmap_bytes(self.n, self.n_ids, self.nlist, self.reverse)
+        self.blob = torch.empty(self.nbytes, dtype=torch.uint8, device=offsets.device)
+        check(lib().pqh_idmap_build(ctx.ptr, _ptr(perm), _ptr(offsets), self.n, self.nlist,
+                                    self.n_ids, int(self.reverse), _ptr(self.blob), self.nbytes),
+              "pqh_idmap_build")
+
+    def _out(self, shape, out):
+        torch = _torch()
+        if out is None:
+            return torch.empty(shape, dtype=torch.int64, device=self.blob.device)
+        if out.dtype != torch.int64 or out.shape != shape or not out.is_contiguous():
+            raise PqhError(-1, f"IdMap: out is a contiguous int64 tensor of shape {tuple(shape)}")
+        return out
+
+    def ids(self, rows, out=None):
+        """the ids of the stream rows `rows` (device int64, any shape, any order, repeats
+        allowed); a negative row is copied through, as the -1 padding of a search result is.
+        Async; ivf_status reports a row >= n (its id is -1)."""
+        torch = _torch()
+        if rows.dtype != torch.int64:
+            raise PqhError(-1, "IdMap.ids: rows is an int64 tensor")
+        rows = rows.contiguous()
+        out = self._out(rows.shape, out)
+        check(lib().pqh_idmap_ids(self.ctx.ptr, _ptr(self.blob), _ptr(rows), rows.numel(),
+                                  _ptr(out)), "pqh_idmap_ids")
+        return out
+
+    def rows(self, ids, offsets=None, out=None):
+        """the stream rows of `ids` (device int64, any shape), -1 for an id without a row (one a
+        compact() dropped); offsets: the lists' (default: those the map was built from).  Needs
+        the reverse part.  Async; ivf_status reports an id outside [0, n_ids) (its row is -1)."""
+        torch = _torch()
+        if not self.reverse:
+            raise PqhError(-1, "IdMap.rows: the map was built with reverse=False")
+        offsets = self.offsets if offsets is None else offsets
+        if (offsets.dtype != torch.int64 or not offsets.is_contiguous() or
+                offsets.numel() != self.nlist + 1):
+            raise PqhError(-1, "IdMap.rows: offsets is a contiguous int64 tensor of nlist + 1 entries")
+        if ids.dtype != torch.int64:
+            raise PqhError(-1, "IdMap.rows: ids is an int64 tensor")
+        ids = ids.contiguous()
+        out = self._out(ids.shape, out)
+        check(lib().pqh_idmap_rows(self.ctx.ptr, _ptr(self.blob), _ptr(offsets), _ptr(ids),
+                                   ids.numel(), _ptr(out)), "pqh_idmap_rows")
+        return out
+
+    def decode(self, first: int = 0, count: int = None, out=None):
+        """the ids of the rows first ... first + count - 1 (count None: up to the last): perm, or
+        a slice of it.  Async."""
+        count = self.n - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.n:
+            raise PqhError(-1, f"IdMap.decode: rows [{first}, {first + count}) of {self.n}")
+        out = self._out((count,), out)
+        check(lib().pqh_idmap_decode(self.ctx.ptr, _ptr(self.blob), first, count, _ptr(out)),
+              "pqh_idmap_decode")
+        return out
+
+    def pack_mask(self, keep, out=None):
+        """pack_mask(ctx, keep, perm) without perm: int32 (ceil(n / 32),), bit s & 31 of word
+        s >> 5 = keep[id of row s].  keep: device bool or uint8 (n_ids,).  Async."""
+        torch = _torch()
+        if keep.dtype not in (torch.bool, torch.uint8) or keep.shape != (self.n_ids,):
+            raise PqhError(-1, "IdMap.pack_mask: keep is a bool or uint8 tensor of shape (n_ids,)")
+        keep = keep.contiguous()
+        if out is None:
+            out = torch.empty((self.n + 31) // 32, dtype=torch.int32, device=self.blob.device)
+        elif (out.dtype != torch.int32 or not out.is_contiguous() or
+              out.numel() != (self.n + 31) // 32):
+            raise PqhError(-1, "IdMap.pack_mask: out is a contiguous int32 tensor of ceil(n / 32) words")
+        check(lib().pqh_mask_pack_idmap(self.ctx.ptr, _ptr(keep), _ptr(self.blob), self.n,
+                                        _ptr(out)), "pqh_mask_pack_idmap")
+        return out
 
 
 class IVF:
@@ -1216,6 +1322,10 @@ class IVF:
     range_search(queries, nprobe, radius) returns every row of the probed lists closer than
     radius, as many as there are (CSR: lims, dist, ids), where search() returns the k nearest.
 
+    build(compress_ids=True) or compress_ids() keeps the ids as an IdMap (idmap; perm and inv
+    are then None): 16 bytes a row become a few bits a row and a list number per id, and every
+    method returns the same bits.  id_bytes() is what the ids cost either way.
+
     Every stage is a call on the context's stream.  search() never waits for the device;
     range_search() waits once per slab of queries (once on a plain index), for the number of
     hits it has to allocate; build(), add() and compact() wait where encode() does, once per
@@ -1232,6 +1342,7 @@ class IVF:
     def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets, residual=False):
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
         self.perm, self.inv, self.offsets = perm, inv, offsets
+        self.idmap = None           # compress_ids(): an IdMap in place of perm and inv
         self.n_ids = perm.numel()   # ids ever given out: inv's length; perm's until a compact()
         self.residual = residual
         self.refine_pq = self.refine_tables = self.refine_enc = None   # build(refine_pq=...)
@@ -1241,12 +1352,13 @@ class IVF:
     @classmethod
     def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
               context: bool = True, residual: bool = False, refine_pq: PQ = None,
-              refine_chunk_vectors: int = None) -> "IVF":
+              refine_chunk_vectors: int = None, compress_ids: bool = False) -> "IVF":
         """x: device float32 (n, d), d = coarse.d = pq.m * pq.dsub.  The stages: rows to
         lists, layout, gather x[perm] (residual: coarse.residuals(x, lists, perm) in its
         place), pq.assign, histogram, Tables.build, encode.  refine_pq: what pq leaves over
         (rows - pq.reconstruct(codes), in place) goes through the same four stages with
-        refine_pq, in chunks of refine_chunk_vectors (default: chunk_vectors)."""
+        refine_pq, in chunks of refine_chunk_vectors (default: chunk_vectors).  compress_ids:
+        the index keeps its ids as an IdMap (compress_ids())."""
         torch = _torch()
         if pq.k > 256 or pq.m > 16:
             raise PqhError(-4, "IVF.build: the search takes K <= 256 and m <= 16")
@@ -1278,7 +1390,50 @@ class IVF:
         ivf = cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
         if refined is not None:
             ivf.refine_pq, (ivf.refine_tables, ivf.refine_enc) = refine_pq, refined
+        if compress_ids:
+            ivf.compress_ids()
         return ivf
+
+    def compress_ids(self) -> int:
+        """keep the ids as an IdMap (Elias-Fano, with the reverse part) in place of perm and inv,
+        which become None; returns the bytes freed.  Every method gives the same bits as before;
+        the lookups at the end of a search are one launch, keep= is packed through the map, and
+        add() and compact() decode perm for the length of the call and build a new map.  On an
+        index that is compressed already nothing is touched.  Async; ivf_status would report
+        ids that do not ascend inside a list, which no index of build(), add() and compact()
+        has."""
+        if self.idmap is not None:
+            return 0
+        before = self.id_bytes()
+        self.idmap = IdMap(self.ctx, self.perm, self.offsets, self.n_ids)
+        self.perm = self.inv = None
+        return before - self.id_bytes()
+
+    def id_bytes(self) -> int:
+        """the bytes of the id structures the index holds: perm and inv, or the IdMap"""
+        if self.idmap is not None:
+            return self.idmap.nbytes
+        return (self.perm.numel() * self.perm.element_size() +
+                self.inv.numel() * self.inv.element_size())
+
+    def _ids_of(self, rows, padded: bool = True):
+        """stream rows to ids; padded: rows may hold the -1 of a search result"""
+        torch = _torch()
+        if self.idmap is not None:
+            return self.idmap.ids(rows)
+        if not padded:
+            return self.perm[rows]
+        return torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
+
+    def _rows_of(self, ids):
+        """ids to stream rows (-1: an id a compact() dropped)"""
+        if self.idmap is not None:
+            return self.idmap.rows(ids, self.offsets)
+        return self.inv[ids]
+
+    def _perm(self):
+        """perm, decoded for the length of a call where the index holds an IdMap"""
+        return self.perm if self.idmap is None else self.idmap.decode()
 
     def remove(self, ids) -> None:
         """take the caller rows `ids` (device int64, each in [0, n)) out of every later search,
@@ -1288,9 +1443,9 @@ class IVF:
         compact() has dropped.  Async, but for the pass over such ids on a compacted index."""
         torch = _torch()
         if self.live is None:
-            self.live = torch.ones(self.perm.numel(), dtype=torch.bool, device=self.perm.device)
-        rows = self.inv[ids.reshape(-1)]
-        if self.perm.numel() != self.n_ids:   # compacted: a dropped id has no row
+            self.live = torch.ones(self.enc.n, dtype=torch.bool, device=self.offsets.device)
+        rows = self._rows_of(ids.reshape(-1))
+        if self.enc.n != self.n_ids:   # compacted: a dropped id has no row
             rows = rows[rows >= 0]
         self.live[rows] = False
         self._live_words = pack_mask(self.ctx, self.live)
@@ -1312,7 +1467,7 @@ class IVF:
         """(tables, enc) of the stream `enc` taken through the plan `dest` into n_new rows, with
         `codes` stored at rows `slots`: decode_scatter, histogram, Tables.build, encode"""
         torch = _torch()
-        merged = torch.empty((n_new, tables.m), dtype=torch.uint8, device=self.perm.device)
+        merged = torch.empty((n_new, tables.m), dtype=torch.uint8, device=self.offsets.device)
         decode_scatter(self.ctx, tables, enc, dest, merged)
         if slots is not None:
             merged[slots] = codes
@@ -1326,7 +1481,7 @@ class IVF:
         """both streams through one plan (ivf_regroup with the mask `keep` and the batch's
         offsets); returns what replaces the index's state, which is touched by the caller only"""
         torch = _torch()
-        n = self.perm.numel()
+        n = self.enc.n
         new_offsets, dest, add_base = ivf_regroup(
             self.ctx, self.offsets, keep, None if batch is None else batch[1], n=n)
         slots = codes = codes2 = None
@@ -1341,10 +1496,15 @@ class IVF:
         ivf_status(self.ctx)
         return new_offsets, dest, slots, level1, level2
 
-    def _commit(self, new_offsets, perm, live, level1, level2):
+    def _commit(self, n_ids: int, new_offsets, perm, live, level1, level2):
         torch = _torch()
-        inv = torch.full((self.n_ids,), -1, dtype=torch.int64, device=perm.device)
-        inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
+        if self.idmap is not None:   # a new map of the new perm: never patched, B and L may change
+            idmap, perm, inv = IdMap(self.ctx, perm, new_offsets, n_ids), None, None
+        else:
+            idmap = None
+            inv = torch.full((n_ids,), -1, dtype=torch.int64, device=perm.device)
+            inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
+        self.n_ids, self.idmap = n_ids, idmap
         self.tables, self.enc = level1
         if level2 is not None:
             self.refine_tables, self.refine_enc = level2
@@ -1369,18 +1529,17 @@ class IVF:
             return first
         if x.dim() != 2 or x.shape[1] != self.coarse.d:
             raise PqhError(-1, "IVF.add: x, the coarse centroids and the PQ disagree in d")
-        n = self.perm.numel()
+        n = self.enc.n
         batch = self._stage_batch(x)
         new_offsets, dest, slots, level1, level2 = self._rebuild(None, batch, n + n_add)
-        perm = torch.empty(n + n_add, dtype=torch.int64, device=self.perm.device)
-        perm[dest] = self.perm
+        perm = torch.empty(n + n_add, dtype=torch.int64, device=self.offsets.device)
+        perm[dest] = self._perm()
         perm[slots] = batch[0] + first
         live = None
         if self.live is not None:
-            live = torch.ones(n + n_add, dtype=torch.bool, device=self.perm.device)
+            live = torch.ones(n + n_add, dtype=torch.bool, device=self.offsets.device)
             live[dest] = self.live
-        self.n_ids = first + n_add
-        self._commit(new_offsets, perm, live, level1, level2)
+        self._commit(first + n_add, new_offsets, perm, live, level1, level2)
         return first
 
     def compact(self) -> int:
@@ -1393,17 +1552,17 @@ class IVF:
         once per stream, and once for the count.  A PqhError leaves the index as it was."""
         if self.live is None:
             return 0
-        n = self.perm.numel()
+        n = self.enc.n
         n_live = int(self.live.sum().item())
         if n_live == n:
             return 0
         new_offsets, _, _, level1, level2 = self._rebuild(self._live_words, None, n_live)
-        self._commit(new_offsets, self.perm[self.live], None, level1, level2)
+        self._commit(self.n_ids, new_offsets, self._perm()[self.live], None, level1, level2)
         return n - n_live
 
     def live_count(self) -> int:
         """the rows remove() has left (synchronises once a row was removed)"""
-        return self.perm.numel() if self.live is None else int(self.live.sum().item())
+        return self.enc.n if self.live is None else int(self.live.sum().item())
 
     def _mask(self, keep):
         """the words of keep (bool over the ids, packed through perm into stream order) ANDed
@@ -1413,7 +1572,9 @@ class IVF:
             return self._live_words
         if keep.dtype != torch.bool or keep.shape != (self.n_ids,):
             raise PqhError(-1, "IVF.search: keep is a bool tensor of shape (n_ids,)")
-        if self.perm.numel() == self.n_ids:
+        if self.idmap is not None:
+            words = self.idmap.pack_mask(keep)
+        elif self.perm.numel() == self.n_ids:
             words = pack_mask(self.ctx, keep, self.perm)
         else:   # compacted: fewer rows than ids, so the gather comes first
             words = pack_mask(self.ctx, keep[self.perm])
@@ -1451,7 +1612,7 @@ class IVF:
         if self.residual:
             dist, rows = self._search_residual(queries, nprobe, k, by_list, mask,
                                                top_k if refine else 0)
-            return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
+            return dist, self._ids_of(rows)
         lut = adc_tables(self.ctx, self.pq, queries)
         range_ptr, ranges, probes, _ = self.coarse.probe(queries, nprobe, self.offsets,
                                                          lists=by_list)
@@ -1463,7 +1624,7 @@ class IVF:
                                        keep=mask)
         if refine:
             dist, rows = self._refine(queries, rows, top_k)
-        return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
+        return dist, self._ids_of(rows)
 
     def _refine(self, queries, rows, k: int, out=None):
         """(dist, stream rows): the k best of the scan's candidate rows by both levels' codes"""
@@ -1527,7 +1688,7 @@ class IVF:
             range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False)
             lims, dist, rows = range_search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr,
                                                    ranges, radius, keep=mask)
-            return lims, dist, self.perm[rows]
+            return lims, dist, self._ids_of(rows, padded=False)
         per_query = nprobe * self.pq.m * self.pq.k * 4
         slab = max(1, min(max(nq, 1), int(self.table_budget) // per_query))
         lut = torch.empty((slab * nprobe, self.pq.m, self.pq.k), dtype=torch.float32,
@@ -1547,7 +1708,7 @@ class IVF:
             return (lims, torch.empty(0, dtype=torch.float32, device=queries.device),
                     torch.empty(0, dtype=torch.int64, device=queries.device))
         dist = torch.cat([p[0] for p in parts])
-        return lims, dist, self.perm[torch.cat([p[1] for p in parts])]
+        return lims, dist, self._ids_of(torch.cat([p[1] for p in parts]), padded=False)
 
     def fetch(self, ids, out=None, refined: bool = False):
         """the reconstructed vectors of caller rows `ids` (device int64, each in [0, n)): what
@@ -1561,7 +1722,7 @@ class IVF:
         torch = _torch()
         if refined and self.refine_pq is None:
             raise PqhError(-1, "IVF.fetch: refined=True on an index built without refine_pq")
-        rows = self.inv[ids.reshape(-1)]
+        rows = self._rows_of(ids.reshape(-1))
         out = fetch(self.ctx, self.tables, self.pq, self.enc, rows, out)
         if refined:
             out[:, :self.coarse.d] += fetch(self.ctx, self.refine_tables, self.refine_pq,
