@@ -745,9 +745,49 @@ int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n], nonzero = 
 
 /* Synchronises; PQH_ERR_ARG if a pqh_ivf_layout / pqh_coarse_probe / pqh_ivf_residuals /
  * pqh_mask_pack / pqh_adc_tables_residual / pqh_ivf_regroup / pqh_idmap_* / pqh_mask_pack_idmap
- * on this context since the last call met a bad value (sticky until read, like
+ * (or the _ip form of one of them) on this context since the last call met a bad value (sticky until read, like
  * pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
+
+/* ---- inner-product search: the metric around the scan -----------------------------------
+ * The scans order plain fp32 sums with `<`, so a maximum-inner-product search scores a pair with
+ * the NEGATED inner product: smaller is nearer, results are ordered by (score, id) ascending
+ * and padded with (+inf, -1) as everywhere else, pqh_range_*'s strict `dist < radius` reads
+ * `ip > -radius`, and a caller's score is -dist.  The arithmetic, for a query slice x and a
+ * vector y of length L:
+ *   nip(x, y):  acc = +0.0f;  for j = 0 ... L - 1 ascending:  acc = acc - x[j] * y[j]
+ * one fp32 multiply and one fp32 subtract per element, no contraction, no final negation, no
+ * reordering (so the sign of a zero is defined too).
+ * Each call takes the arguments of its L2 twin and has the twin's conventions, limits, argument
+ * errors and device errors (pqh_ivf_status, pqh_decode_status); nq == 0 or n == 0 launches
+ * nothing.  The scan calls (pqh_search_*, pqh_range_*) take these tables unchanged. */
+/* lut[q][i][c] = nip(query[q][i*dsub ...], cent[i][c]) -- see pqh_adc_tables. */
+int pqh_adc_tables_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
+                      long long ld_q, float* d_lut);
+/* d_list[v] = the first l that minimises nip(x[v], c[l]), one chain over all d dimensions (ties
+ * go to the smaller l); d_dist (optional) that value -- see pqh_coarse_assign. */
+int pqh_coarse_assign_ip(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
+                         long long ld_x, int32_t* d_list, float* d_dist);
+/* The nprobe lists by (nip(q, c[l]), l) ascending; the four outputs and the padding of
+ * pqh_coarse_probe, d_probe_dist holding the nip values (bit-equal to pqh_coarse_assign_ip's
+ * d_dist for nprobe == 1). */
+int pqh_coarse_probe_ip(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_queries,
+                        long long nq, long long ld_q, int nprobe, const long long* d_offsets,
+                        long long* d_range_ptr, long long* d_ranges, long long* d_probes,
+                        float* d_probe_dist);
+/* One table per (query, probed list) of a residual index (the stream holds the codes of
+ * x - c[list]) for pqh_search_*_range_tables and pqh_search_*_lists: <q, c[l] + r> is
+ * <q, c[l]> + <q, r>, so with l = d_probes[q][p], bias = nip(query[q], c[l]) over all d
+ * dimensions and plain = pqh_adc_tables_ip's table of query q,
+ *   d_lut[q * nprobe + p][i][c] = plain[q][i][c]                 for i >= 1
+ *   d_lut[q * nprobe + p][0][c] = bias + plain[q][0][c]          (one fp32 add)
+ * bias is pqh_coarse_probe_ip's d_probe_dist for that pair on every bit.  l == -1 gives a table
+ * of +inf; any other l outside [0, nlist) the same and PQH_ERR_ARG from pqh_ivf_status.
+ * Argument errors and limits are pqh_adc_tables_residual's. */
+int pqh_adc_tables_residual_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse_t* cq,
+                               const float* d_queries, long long nq, long long ld_q,
+                               const long long* d_probes /* [nq][nprobe] */, int nprobe,
+                               float* d_lut /* [nq * nprobe][m][K] */);
 
 /* ---- a mutable inverted file: a list-ordered stream taken to a new list order ------------
  * The streams hold everything an index is rebuilt from.  pqh_ivf_regroup plans the new order
@@ -909,6 +949,29 @@ int pqh_refine_codes(pqh_ctx_t* ctx, const pqh_pq_t* pq1, const void* d_codes1,
                      const pqh_coarse_t* cq, const long long* d_offsets, const float* d_queries,
                      long long nq, long long ld_q, const long long* d_rows /* [nq][ncand] */,
                      int ncand, int top_k, float* d_dist, long long* d_ids, long long ld_out);
+
+/* The re-rank by inner product: y = cent1[..][j] + cent2[..][j] (one add; residual index:
+ * y[j] = c[l][j] + y[j], one more add, l the row's list as above) and dist = nip(query, y), one
+ * chain over d (the definition of nip is with pqh_adc_tables_ip).  Candidate checks, padding,
+ * ld_out, both candidate widths, limits and error precedence are pqh_refine_stream's and
+ * pqh_refine_codes'. */
+int pqh_refine_stream_ip(pqh_ctx_t* ctx, const pqh_tables_t* t1, const pqh_pq_t* pq1,
+                         const unsigned char* d_stream1, unsigned long long stream_bytes1,
+                         int raw_first1, int chunk_vectors1,
+                         const unsigned long long* d_chunk_offsets1, const void* d_chunk_prev1,
+                         const pqh_tables_t* t2, const pqh_pq_t* pq2,
+                         const unsigned char* d_stream2, unsigned long long stream_bytes2,
+                         int raw_first2, int chunk_vectors2,
+                         const unsigned long long* d_chunk_offsets2, const void* d_chunk_prev2,
+                         long long n, const pqh_coarse_t* cq, const long long* d_offsets,
+                         const float* d_queries, long long nq, long long ld_q,
+                         const long long* d_rows /* [nq][ncand] */, int ncand, int top_k,
+                         float* d_dist, long long* d_ids, long long ld_out);
+int pqh_refine_codes_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq1, const void* d_codes1,
+                        const pqh_pq_t* pq2, const void* d_codes2, long long n,
+                        const pqh_coarse_t* cq, const long long* d_offsets, const float* d_queries,
+                        long long nq, long long ld_q, const long long* d_rows /* [nq][ncand] */,
+                        int ncand, int top_k, float* d_dist, long long* d_ids, long long ld_out);
 
 /* Build the chunk index of an existing stream (one produced without a sidecar, e.g. by
  * the reference encoder) with a sequential table walk on the HOST copy of the stream

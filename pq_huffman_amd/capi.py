@@ -212,6 +212,15 @@ SIGNATURES = [
      [P, P, P, P, ULL, I, I, P, P, P, P, P, ULL, I, I, P, P, LL, P, P, P, LL, LL, P, I, I, P, P,
       LL]),
     ("pqh_refine_codes", I, [P, P, P, P, P, LL, P, P, P, LL, LL, P, I, I, P, P, LL]),
+    # the inner-product forms: the arguments of their L2 twins
+    ("pqh_adc_tables_ip", I, [P, P, P, LL, LL, P]),
+    ("pqh_coarse_assign_ip", I, [P, P, P, LL, LL, P, P]),
+    ("pqh_coarse_probe_ip", I, [P, P, P, LL, LL, I, P, P, P, P, P]),
+    ("pqh_adc_tables_residual_ip", I, [P, P, P, P, LL, LL, P, I, P]),
+    ("pqh_refine_stream_ip", I,
+     [P, P, P, P, ULL, I, I, P, P, P, P, P, ULL, I, I, P, P, LL, P, P, P, LL, LL, P, I, I, P, P,
+      LL]),
+    ("pqh_refine_codes_ip", I, [P, P, P, P, P, LL, P, P, P, LL, LL, P, I, I, P, P, LL]),
     ("pqh_decode_status", I, [P]), ("pqh_encode_status", I, [P]),
     ("pqh_chunk_index_host", I, [P, P, ULL, LL, I, I, P, P]),
     ("pqh_sort_rows", I, [P, P, LL, I, P]),

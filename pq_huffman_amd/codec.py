@@ -668,6 +668,15 @@ def pq_residuals(ctx: Context, pq: PQ, x, codes=None):
     return x[:, :pq.m * pq.dsub].clone().sub_(pq.reconstruct(codes))
 
 
+def _metric_suffix(metric, what: str) -> str:
+    """"" for metric "l2", "_ip" for "ip" (the name of the C call), PqhError(-1) otherwise"""
+    if metric == "l2":
+        return ""
+    if metric == "ip":
+        return "_ip"
+    raise PqhError(-1, f"{what}: metric {metric!r} (\"l2\" or \"ip\")")
+
+
 def _refine_level(level):
     """(is a stream, n, the level's arguments in pqh.h order) of (tables, pq, enc) or (pq, codes)"""
     if len(level) == 3:
@@ -693,7 +702,21 @@ def refine(ctx: Context, level1, level2, queries, rows, k: int, coarse: "Coarse"
     loses the centroid of the row's list first).  out: a (dist, rows) pair to fill, rows
     out[0].stride(0) apart in both.  Async; decode_status reports a row outside [0, n)
     (dropped) and a corrupt stream."""
+    return _refine(ctx, level1, level2, queries, rows, k, coarse, offsets, out, "l2")
+
+
+def refine_ip(ctx: Context, level1, level2, queries, rows, k: int, coarse: "Coarse" = None,
+              offsets=None, out=None):
+    """refine() by inner product: dist is the negated inner product of the query and the sum of
+    both levels' reconstructions (residual index: the centroid of the row's list added to that
+    sum), acc = acc - q[j] * y[j] over all d dimensions in order (pqh_refine_stream_ip,
+    pqh_refine_codes_ip).  Arguments, order, padding and errors are refine()'s."""
+    return _refine(ctx, level1, level2, queries, rows, k, coarse, offsets, out, "ip")
+
+
+def _refine(ctx, level1, level2, queries, rows, k, coarse, offsets, out, metric):
     torch = _torch()
+    sfx = _metric_suffix(metric, "refine")
     s1, n1, a1 = _refine_level(level1)
     s2, n2, a2 = _refine_level(level2)
     if s1 != s2 or n1 != n2:
@@ -713,22 +736,23 @@ def refine(ctx: Context, level1, level2, queries, rows, k: int, coarse: "Coarse"
         raise PqhError(-1, "refine: out is a pair of tensors with rows the same distance apart")
     tail = (n1, coarse.ptr if coarse is not None else None, _ptr(offsets), _ptr(queries), nq,
             queries.stride(0), _ptr(rows), ncand, k, _ptr(dist), _ptr(ids), ld)
-    if s1:
-        check(lib().pqh_refine_stream(ctx.ptr, *a1, *a2, *tail), "pqh_refine_stream")
-    else:
-        check(lib().pqh_refine_codes(ctx.ptr, *a1, *a2, *tail), "pqh_refine_codes")
+    name = ("pqh_refine_stream" if s1 else "pqh_refine_codes") + sfx
+    check(getattr(lib(), name)(ctx.ptr, *a1, *a2, *tail), name)
     return dist, ids
 
 
-def adc_tables(ctx: Context, pq: PQ, queries, out=None):
+def adc_tables(ctx: Context, pq: PQ, queries, out=None, metric: str = "l2"):
     """the ADC tables of `queries` (device float32 (nq, >= m * dsub)): float32 (nq, m, K),
-    lut[q][i][c] = ||q_i - cent[i][c]||^2 in the assignment's arithmetic (pqh_adc_tables)."""
+    lut[q][i][c] = ||q_i - cent[i][c]||^2 in the assignment's arithmetic (pqh_adc_tables).
+    metric="ip": lut[q][i][c] = the negated inner product of q_i and cent[i][c],
+    acc = acc - q[j] * c[j] in order (pqh_adc_tables_ip); every scan takes either kind."""
     torch = _torch()
+    name = "pqh_adc_tables" + _metric_suffix(metric, "adc_tables")
     nq = queries.shape[0]
     if out is None:
         out = torch.empty((nq, pq.m, pq.k), dtype=torch.float32, device=queries.device)
-    check(lib().pqh_adc_tables(ctx.ptr, pq.ptr, _ptr(queries), nq, queries.stride(0), _ptr(out)),
-          "pqh_adc_tables")
+    check(getattr(lib(), name)(ctx.ptr, pq.ptr, _ptr(queries), nq, queries.stride(0), _ptr(out)),
+          name)
     return out
 
 
@@ -827,21 +851,25 @@ def search_codes_ranges(ctx: Context, codes, lut, range_ptr, ranges, k: int, id_
     return dist, ids
 
 
-def adc_tables_residual(ctx: Context, pq: PQ, coarse: "Coarse", queries, probes, out=None):
+def adc_tables_residual(ctx: Context, pq: PQ, coarse: "Coarse", queries, probes, out=None,
+                        metric: str = "l2"):
     """one ADC table per (query, probed list): float32 (nq * nprobe, m, K), table q * nprobe + p
     that of queries[q] - centroid[probes[q, p]] in adc_tables' arithmetic
     (pqh_adc_tables_residual).  probes: device int64 (nq, nprobe) as Coarse.probe returns them;
     an entry of -1 gives a table of +inf.  Async; ivf_status reports any other entry outside
-    [0, nlist)."""
+    [0, nlist).
+    metric="ip": table q * nprobe + p is adc_tables(metric="ip") of queries[q] with the negated
+    inner product of queries[q] and centroid[probes[q, p]] (Coarse.probe's probe_dist, bit for
+    bit) added to every entry of part 0 (pqh_adc_tables_residual_ip)."""
     torch = _torch()
+    name = "pqh_adc_tables_residual" + _metric_suffix(metric, "adc_tables_residual")
     nq, nprobe = probes.shape
     if not probes.is_contiguous():
         probes = probes.contiguous()
     if out is None:
         out = torch.empty((nq * nprobe, pq.m, pq.k), dtype=torch.float32, device=queries.device)
-    check(lib().pqh_adc_tables_residual(ctx.ptr, pq.ptr, coarse.ptr, _ptr(queries), nq,
-                                        queries.stride(0), _ptr(probes), nprobe, _ptr(out)),
-          "pqh_adc_tables_residual")
+    check(getattr(lib(), name)(ctx.ptr, pq.ptr, coarse.ptr, _ptr(queries), nq, queries.stride(0),
+                               _ptr(probes), nprobe, _ptr(out)), name)
     return out
 
 
@@ -1068,16 +1096,18 @@ class Coarse:
         # a device copy for torch (the fetch of a residual index adds a row's centroid back)
         self.centroids = _torch().tensor(c, device=f"cuda:{ctx.device}")
 
-    def assign(self, x, out=None, dist=None):
+    def assign(self, x, out=None, dist=None, metric: str = "l2"):
         """list ids int32 (n,) of the rows of x (device float32 (n, >= d)), the nearest
         centroid each (pqh_coarse_assign); dist: an optional float32 (n,) tensor that takes the
-        winning distances.  Async."""
+        winning distances.  metric="ip": the centroid of the largest inner product, dist its
+        negation (pqh_coarse_assign_ip).  Async."""
         torch = _torch()
+        name = "pqh_coarse_assign" + _metric_suffix(metric, "Coarse.assign")
         n = x.shape[0]
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=x.device)
-        check(lib().pqh_coarse_assign(self.ctx.ptr, self.ptr, _ptr(x), n, x.stride(0), _ptr(out),
-                                      _ptr(dist)), "pqh_coarse_assign")
+        check(getattr(lib(), name)(self.ctx.ptr, self.ptr, _ptr(x), n, x.stride(0), _ptr(out),
+                                   _ptr(dist)), name)
         return out
 
     def layout(self, list_ids):
@@ -1112,22 +1142,24 @@ class Coarse:
               "pqh_ivf_residuals")
         return out
 
-    def probe(self, queries, nprobe: int, offsets, lists: bool = True):
+    def probe(self, queries, nprobe: int, offsets, lists: bool = True, metric: str = "l2"):
         """(range_ptr, ranges, probes, probe_dist): for every query (device float32
         (nq, >= d)) its nprobe nearest lists by (dist, list id) and their row ranges in the CSR
         form search_ranges takes (pqh_coarse_probe).  probes int64 (nq, nprobe) and probe_dist
         float32 (nq, nprobe), padded with (-1, +inf) and the range (0, 0) when nprobe > nlist;
-        lists=False leaves the two out (None).  Async, no sync."""
+        lists=False leaves the two out (None).  metric="ip": the lists of the largest inner
+        products, probe_dist their negations (pqh_coarse_probe_ip).  Async, no sync."""
         torch = _torch()
+        name = "pqh_coarse_probe" + _metric_suffix(metric, "Coarse.probe")
         nq = queries.shape[0]
         dev = queries.device
         range_ptr = torch.empty(nq + 1, dtype=torch.int64, device=dev)
         ranges = torch.empty((nq * nprobe, 2), dtype=torch.int64, device=dev)
         probes = torch.empty((nq, nprobe), dtype=torch.int64, device=dev) if lists else None
         pdist = torch.empty((nq, nprobe), dtype=torch.float32, device=dev) if lists else None
-        check(lib().pqh_coarse_probe(self.ctx.ptr, self.ptr, _ptr(queries), nq, queries.stride(0),
-                                     nprobe, _ptr(offsets), _ptr(range_ptr), _ptr(ranges),
-                                     _ptr(probes), _ptr(pdist)), "pqh_coarse_probe")
+        check(getattr(lib(), name)(self.ctx.ptr, self.ptr, _ptr(queries), nq, queries.stride(0),
+                                   nprobe, _ptr(offsets), _ptr(range_ptr), _ptr(ranges),
+                                   _ptr(probes), _ptr(pdist)), name)
         return range_ptr, ranges, probes, pdist
 
     def close(self):
@@ -1326,6 +1358,14 @@ class IVF:
     are then None): 16 bytes a row become a few bits a row and a list number per id, and every
     method returns the same bits.  id_bytes() is what the ids cost either way.
 
+    build(metric="ip") makes a maximum-inner-product index: rows go to the list of the largest
+    inner product, every stage of search() and range_search() scores with the negated inner
+    product (scores = -dist: smaller is still nearer, the order, the padding and the strict
+    `dist < radius` are unchanged), and add() assigns its rows the same way.  The stream of a
+    residual index still holds the codes of x - centroid[list]; its per-(query, list) tables
+    are the query's plain table with the list's score folded into part 0.  The scans, the
+    filters, remove(), compact(), compress_ids() and fetch() are the same code for both metrics.
+
     Every stage is a call on the context's stream.  search() never waits for the device;
     range_search() waits once per slab of queries (once on a plain index), for the number of
     hits it has to allocate; build(), add() and compact() wait where encode() does, once per
@@ -1339,12 +1379,14 @@ class IVF:
     # the query-major form stays ahead up to a ratio of 32.
     list_major_ratio = 4.0
 
-    def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets, residual=False):
+    def __init__(self, ctx, pq, coarse, tables, enc, perm, inv, offsets, residual=False,
+                 metric="l2"):
         self.ctx, self.pq, self.coarse, self.tables, self.enc = ctx, pq, coarse, tables, enc
         self.perm, self.inv, self.offsets = perm, inv, offsets
         self.idmap = None           # compress_ids(): an IdMap in place of perm and inv
         self.n_ids = perm.numel()   # ids ever given out: inv's length; perm's until a compact()
         self.residual = residual
+        self.metric = metric        # "l2" or "ip": how rows go to lists and how a search scores
         self.refine_pq = self.refine_tables = self.refine_enc = None   # build(refine_pq=...)
         self.live = None         # remove(): device bool per stream row, allocated on first use
         self._live_words = None  # its packed form, made again after a remove()
@@ -1352,14 +1394,17 @@ class IVF:
     @classmethod
     def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
               context: bool = True, residual: bool = False, refine_pq: PQ = None,
-              refine_chunk_vectors: int = None, compress_ids: bool = False) -> "IVF":
+              refine_chunk_vectors: int = None, compress_ids: bool = False,
+              metric: str = "l2") -> "IVF":
         """x: device float32 (n, d), d = coarse.d = pq.m * pq.dsub.  The stages: rows to
         lists, layout, gather x[perm] (residual: coarse.residuals(x, lists, perm) in its
         place), pq.assign, histogram, Tables.build, encode.  refine_pq: what pq leaves over
         (rows - pq.reconstruct(codes), in place) goes through the same four stages with
         refine_pq, in chunks of refine_chunk_vectors (default: chunk_vectors).  compress_ids:
-        the index keeps its ids as an IdMap (compress_ids())."""
+        the index keeps its ids as an IdMap (compress_ids()).  metric: "l2" or "ip" (see the
+        class)."""
         torch = _torch()
+        _metric_suffix(metric, "IVF.build")
         if pq.k > 256 or pq.m > 16:
             raise PqhError(-4, "IVF.build: the search takes K <= 256 and m <= 16")
         if coarse.d != pq.m * pq.dsub or x.shape[1] != coarse.d:
@@ -1369,7 +1414,7 @@ class IVF:
                 raise PqhError(-4, "IVF.build: the re-rank takes K <= 256 and m <= 16")
             if refine_pq.m * refine_pq.dsub != coarse.d:
                 raise PqhError(-1, "IVF.build: refine_pq and the PQ disagree in d")
-        lists = coarse.assign(x)
+        lists = coarse.assign(x, metric=metric)
         perm, offsets = coarse.layout(lists)
         rows = coarse.residuals(x, lists, perm) if residual else x[perm]
         codes = pq.assign(rows, ctx=ctx)
@@ -1387,7 +1432,7 @@ class IVF:
         enc = encode(ctx, tables, codes, chunk_vectors=chunk_vectors)
         inv = torch.empty_like(perm)
         inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
-        ivf = cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual)
+        ivf = cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual, metric)
         if refined is not None:
             ivf.refine_pq, (ivf.refine_tables, ivf.refine_enc) = refine_pq, refined
         if compress_ids:
@@ -1453,7 +1498,7 @@ class IVF:
     def _stage_batch(self, x):
         """(perm, offsets, list of every sorted row, codes, level-2 codes or None) of a batch of
         new rows, the codes in the batch's own list order: the stages of build()"""
-        lists = self.coarse.assign(x)
+        lists = self.coarse.assign(x, metric=self.metric)
         perm, offsets = self.coarse.layout(lists)
         rows = self.coarse.residuals(x, lists, perm) if self.residual else x[perm]
         codes = self.pq.assign(rows, ctx=self.ctx)
@@ -1613,9 +1658,9 @@ class IVF:
             dist, rows = self._search_residual(queries, nprobe, k, by_list, mask,
                                                top_k if refine else 0)
             return dist, self._ids_of(rows)
-        lut = adc_tables(self.ctx, self.pq, queries)
+        lut = adc_tables(self.ctx, self.pq, queries, metric=self.metric)
         range_ptr, ranges, probes, _ = self.coarse.probe(queries, nprobe, self.offsets,
-                                                         lists=by_list)
+                                                         lists=by_list, metric=self.metric)
         if by_list:
             dist, rows = search_lists(self.ctx, self.tables, self.enc, lut, self.offsets, probes, k,
                                       keep=mask)
@@ -1628,10 +1673,10 @@ class IVF:
 
     def _refine(self, queries, rows, k: int, out=None):
         """(dist, stream rows): the k best of the scan's candidate rows by both levels' codes"""
-        return refine(self.ctx, (self.tables, self.pq, self.enc),
-                      (self.refine_tables, self.refine_pq, self.refine_enc), queries, rows, k,
-                      self.coarse if self.residual else None,
-                      self.offsets if self.residual else None, out=out)
+        return _refine(self.ctx, (self.tables, self.pq, self.enc),
+                       (self.refine_tables, self.refine_pq, self.refine_enc), queries, rows, k,
+                       self.coarse if self.residual else None,
+                       self.offsets if self.residual else None, out, self.metric)
 
     def _search_residual(self, queries, nprobe: int, k: int, by_list: bool = False, mask=None,
                          refine_k: int = 0):
@@ -1652,9 +1697,10 @@ class IVF:
                           device=queries.device)
         for s in range(0, nq, slab):
             q = queries[s:s + slab]
-            range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True)
+            range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True,
+                                                             metric=self.metric)
             adc_tables_residual(self.ctx, self.pq, self.coarse, q, probes,
-                                out=lut[:q.shape[0] * nprobe])
+                                out=lut[:q.shape[0] * nprobe], metric=self.metric)
             out = (dist[s:s + slab], rows[s:s + slab])
             if by_list:
                 search_lists(self.ctx, self.tables, self.enc, lut[:q.shape[0] * nprobe],
@@ -1684,8 +1730,9 @@ class IVF:
         else:
             radius = torch.full((nq,), float(radius), dtype=torch.float32, device=queries.device)
         if not self.residual:
-            lut = adc_tables(self.ctx, self.pq, queries)
-            range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False)
+            lut = adc_tables(self.ctx, self.pq, queries, metric=self.metric)
+            range_ptr, ranges, _, _ = self.coarse.probe(queries, nprobe, self.offsets, lists=False,
+                                                        metric=self.metric)
             lims, dist, rows = range_search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr,
                                                    ranges, radius, keep=mask)
             return lims, dist, self._ids_of(rows, padded=False)
@@ -1697,9 +1744,10 @@ class IVF:
         parts = []
         for s in range(0, nq, slab):
             q = queries[s:s + slab]
-            range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True)
+            range_ptr, ranges, probes, _ = self.coarse.probe(q, nprobe, self.offsets, lists=True,
+                                                             metric=self.metric)
             adc_tables_residual(self.ctx, self.pq, self.coarse, q, probes,
-                                out=lut[:q.shape[0] * nprobe])
+                                out=lut[:q.shape[0] * nprobe], metric=self.metric)
             l, d, r = range_search_ranges(self.ctx, self.tables, self.enc, lut, range_ptr, ranges,
                                           radius[s:s + slab], tables_per_range=True, keep=mask)
             lims[s + 1:s + 1 + q.shape[0]] = l[1:] + lims[s]

@@ -379,6 +379,12 @@ int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_
     return PQH_OK;
 }
 
+int pqh_coarse_view_t(const pqh_coarse_t* cq, const float** d_cent_t) {
+    if (!cq) return PQH_ERR_ARG;
+    *d_cent_t = cq->d_cent_t;
+    return PQH_OK;
+}
+
 extern "C" {
 
 int pqh_coarse_create(pqh_ctx_t* ctx, const float* centroids, int nlist, int d, pqh_coarse_t** cq) {

@@ -4,6 +4,10 @@
 //   dist(q, r) = sum_j (q[j] - (c1[a][j] + c2[b][j]))^2      (residual index: q - c[list(r)])
 // in fp32, one add, one (or two) subtracts, one multiply and one add per dimension, j ascending
 // over the whole vector, no contraction.
+// The inner-product form (pqh_refine_*_ip, the IP instantiations) scores the same candidates by
+//   nip(q, r) = acc,  acc = +0;  acc = acc - q[j] * (c1[a][j] + c2[b][j])
+// (residual index: c[list(r)][j] + (c1[a][j] + c2[b][j])), the negated inner product of
+// pqh_metric.hip, one chain over d; decode, select and errors are shared with the L2 form.
 //
 //  refine_rows   one workgroup of two waves per query, one candidate per lane.
 //                Decode: wave 0 reaches the lane's row of the level-1 stream and wave 1 the same
@@ -77,7 +81,7 @@ __device__ __forceinline__ bool level_row(const Level& L, long long v, uint8_t* 
     return good;
 }
 
-template <bool STREAM>
+template <bool STREAM, bool IP>
 __global__ void __launch_bounds__(128)
 refine_rows(Levels P, long long n, const float* __restrict__ coarse, int nlist,
             const long long* __restrict__ offsets, const float* __restrict__ queries,
@@ -144,16 +148,28 @@ refine_rows(Levels P, long long n, const float* __restrict__ coarse, int nlist,
                 const float4 u1 = *reinterpret_cast<const float4*>(c1 + j1);
                 const float4 u2 = *reinterpret_cast<const float4*>(c2 + j2);
                 float4 x = *reinterpret_cast<const float4*>(qs + j);
-                if (cl) {
-                    const float4 cv = *reinterpret_cast<const float4*>(cl + j);
-                    x = make_float4(x.x - cv.x, x.y - cv.y, x.z - cv.z, x.w - cv.w);
+                if constexpr (IP) {
+                    float4 y = make_float4(u1.x + u2.x, u1.y + u2.y, u1.z + u2.z, u1.w + u2.w);
+                    if (cl) {
+                        const float4 cv = *reinterpret_cast<const float4*>(cl + j);
+                        y = make_float4(cv.x + y.x, cv.y + y.y, cv.z + y.z, cv.w + y.w);
+                    }
+                    acc = acc - x.x * y.x;
+                    acc = acc - x.y * y.y;
+                    acc = acc - x.z * y.z;
+                    acc = acc - x.w * y.w;
+                } else {
+                    if (cl) {
+                        const float4 cv = *reinterpret_cast<const float4*>(cl + j);
+                        x = make_float4(x.x - cv.x, x.y - cv.y, x.z - cv.z, x.w - cv.w);
+                    }
+                    const float t0 = x.x - (u1.x + u2.x), t1 = x.y - (u1.y + u2.y),
+                                t2 = x.z - (u1.z + u2.z), t3 = x.w - (u1.w + u2.w);
+                    acc = acc + t0 * t0;
+                    acc = acc + t1 * t1;
+                    acc = acc + t2 * t2;
+                    acc = acc + t3 * t3;
                 }
-                const float t0 = x.x - (u1.x + u2.x), t1 = x.y - (u1.y + u2.y),
-                            t2 = x.z - (u1.z + u2.z), t3 = x.w - (u1.w + u2.w);
-                acc = acc + t0 * t0;
-                acc = acc + t1 * t1;
-                acc = acc + t2 * t2;
-                acc = acc + t3 * t3;
                 j1 += 4;
                 j2 += 4;
                 if (j1 == ds1 && j + 4 < d) ++i1, c1 = cent1 + (i1 * k1 + a[i1]) * ds1, j1 = 0;
@@ -161,11 +177,16 @@ refine_rows(Levels P, long long n, const float* __restrict__ coarse, int nlist,
             }
         } else {
             for (int j = 0; j < d; ++j) {
-                const float y = c1[j1] + c2[j2];
+                float y = c1[j1] + c2[j2];
                 float x = qs[j];
-                if (cl) x = x - cl[j];
-                const float t = x - y;
-                acc = acc + t * t;
+                if constexpr (IP) {
+                    if (cl) y = cl[j] + y;
+                    acc = acc - x * y;
+                } else {
+                    if (cl) x = x - cl[j];
+                    const float t = x - y;
+                    acc = acc + t * t;
+                }
                 if (++j1 == ds1 && j + 1 < d) ++i1, c1 = cent1 + (i1 * k1 + a[i1]) * ds1, j1 = 0;
                 if (++j2 == ds2 && j + 1 < d) ++i2, c2 = cent2 + (i2 * k2 + b[i2]) * ds2, j2 = 0;
             }
@@ -185,6 +206,7 @@ refine_rows(Levels P, long long n, const float* __restrict__ coarse, int nlist,
 // code): the distance of candidate row v, its code rows a and b in LDS, one chain over the d
 // dimensions.  *valid is cleared (and error bit 2 set) for a row past the last list of a
 // residual index.
+template <bool IP>
 __device__ __forceinline__ float cand_dist(const Levels& P, const float* coarse, int nlist,
                                            const long long* offsets, const float* qs, int d,
                                            long long v, const uint8_t* a, const uint8_t* b,
@@ -220,16 +242,28 @@ __device__ __forceinline__ float cand_dist(const Levels& P, const float* coarse,
                 const float4 u1 = *reinterpret_cast<const float4*>(c1 + j1);
                 const float4 u2 = *reinterpret_cast<const float4*>(c2 + j2);
                 float4 x = *reinterpret_cast<const float4*>(qs + j);
-                if (cl) {
-                    const float4 cv = *reinterpret_cast<const float4*>(cl + j);
-                    x = make_float4(x.x - cv.x, x.y - cv.y, x.z - cv.z, x.w - cv.w);
+                if constexpr (IP) {
+                    float4 y = make_float4(u1.x + u2.x, u1.y + u2.y, u1.z + u2.z, u1.w + u2.w);
+                    if (cl) {
+                        const float4 cv = *reinterpret_cast<const float4*>(cl + j);
+                        y = make_float4(cv.x + y.x, cv.y + y.y, cv.z + y.z, cv.w + y.w);
+                    }
+                    acc = acc - x.x * y.x;
+                    acc = acc - x.y * y.y;
+                    acc = acc - x.z * y.z;
+                    acc = acc - x.w * y.w;
+                } else {
+                    if (cl) {
+                        const float4 cv = *reinterpret_cast<const float4*>(cl + j);
+                        x = make_float4(x.x - cv.x, x.y - cv.y, x.z - cv.z, x.w - cv.w);
+                    }
+                    const float t0 = x.x - (u1.x + u2.x), t1 = x.y - (u1.y + u2.y),
+                                t2 = x.z - (u1.z + u2.z), t3 = x.w - (u1.w + u2.w);
+                    acc = acc + t0 * t0;
+                    acc = acc + t1 * t1;
+                    acc = acc + t2 * t2;
+                    acc = acc + t3 * t3;
                 }
-                const float t0 = x.x - (u1.x + u2.x), t1 = x.y - (u1.y + u2.y),
-                            t2 = x.z - (u1.z + u2.z), t3 = x.w - (u1.w + u2.w);
-                acc = acc + t0 * t0;
-                acc = acc + t1 * t1;
-                acc = acc + t2 * t2;
-                acc = acc + t3 * t3;
                 j1 += 4;
                 j2 += 4;
                 if (j1 == ds1 && j + 4 < d) ++i1, c1 = cent1 + (i1 * k1 + a[i1]) * ds1, j1 = 0;
@@ -237,11 +271,16 @@ __device__ __forceinline__ float cand_dist(const Levels& P, const float* coarse,
             }
         } else {
             for (int j = 0; j < d; ++j) {
-                const float y = c1[j1] + c2[j2];
+                float y = c1[j1] + c2[j2];
                 float x = qs[j];
-                if (cl) x = x - cl[j];
-                const float t = x - y;
-                acc = acc + t * t;
+                if constexpr (IP) {
+                    if (cl) y = cl[j] + y;
+                    acc = acc - x * y;
+                } else {
+                    if (cl) x = x - cl[j];
+                    const float t = x - y;
+                    acc = acc + t * t;
+                }
                 if (++j1 == ds1 && j + 1 < d) ++i1, c1 = cent1 + (i1 * k1 + a[i1]) * ds1, j1 = 0;
                 if (++j2 == ds2 && j + 1 < d) ++i2, c2 = cent2 + (i2 * k2 + b[i2]) * ds2, j2 = 0;
             }
@@ -257,7 +296,7 @@ __device__ __forceinline__ float cand_dist(const Levels& P, const float* coarse,
 // workgroup has 2 * ceil(ncand / 64) waves.
 constexpr int kWidePairs = PQH_SEARCH_MAX_K_WIDE / 64;
 static_assert(kWidePairs == kWideKR, "the wide list holds the candidates of every pair");
-template <bool STREAM>
+template <bool STREAM, bool IP>
 __global__ void __launch_bounds__(128 * kWidePairs)
 refine_rows_wide(Levels P, long long n, const float* __restrict__ coarse, int nlist,
                  const long long* __restrict__ offsets, const float* __restrict__ queries,
@@ -295,7 +334,7 @@ refine_rows_wide(Levels P, long long n, const float* __restrict__ coarse, int nl
     // ---- distance: the even waves, one chain over the d dimensions each
     if (lv == 0) {
         bool valid = inside && !dead[0][c] && !dead[1][c];
-        const float acc = cand_dist(P, coarse, nlist, offsets, qs, d, v, &code[0][c * kRowStride],
+        const float acc = cand_dist<IP>(P, coarse, nlist, offsets, qs, d, v, &code[0][c * kRowStride],
                                     &code[1][c * kRowStride], valid, err);
         key_d[c] = valid ? acc : INFINITY;
         key_id[c] = valid ? v : 0x7FFFFFFFFFFFFFFFll;
@@ -364,6 +403,7 @@ int level_of(const LevelArgs& a, bool stream, long long n, bool run, Level* L) {
     return PQH_OK;
 }
 
+template <bool IP>
 int refine(pqh_ctx_t* ctx, bool stream, const LevelArgs& a1, const LevelArgs& a2, long long n,
            const pqh_coarse_t* cq, const long long* d_offsets, const float* d_queries, long long nq,
            long long ld_q, const long long* d_rows, int ncand, int top_k, float* d_dist,
@@ -394,14 +434,17 @@ int refine(pqh_ctx_t* ctx, bool stream, const LevelArgs& a1, const LevelArgs& a2
     const size_t lds = (size_t)d * 4;
     const bool wide = ncand > PQH_SEARCH_MAX_K;   // a wave pair per 64 candidates
     const dim3 block(wide ? 128 * ((ncand + 63) / 64) : 128);
+    // (a name with a comma in it is two arguments to the launch macro: the parentheses)
     if (stream)
-        hipLaunchKernelGGL(wide ? refine_rows_wide<true> : refine_rows<true>, dim3((unsigned)nq),
-                           block, lds, ctx->stream, P, n, d_coarse, nlist, d_offsets, d_queries,
-                           ld_q, d_rows, ncand, top_k, d_dist, d_ids, ld_out, ctx->d_diag + 1);
+        hipLaunchKernelGGL((wide ? refine_rows_wide<true, IP> : refine_rows<true, IP>),
+                           dim3((unsigned)nq), block, lds, ctx->stream, P, n, d_coarse, nlist,
+                           d_offsets, d_queries, ld_q, d_rows, ncand, top_k, d_dist, d_ids, ld_out,
+                           ctx->d_diag + 1);
     else
-        hipLaunchKernelGGL(wide ? refine_rows_wide<false> : refine_rows<false>, dim3((unsigned)nq),
-                           block, lds, ctx->stream, P, n, d_coarse, nlist, d_offsets, d_queries,
-                           ld_q, d_rows, ncand, top_k, d_dist, d_ids, ld_out, ctx->d_diag + 1);
+        hipLaunchKernelGGL((wide ? refine_rows_wide<false, IP> : refine_rows<false, IP>),
+                           dim3((unsigned)nq), block, lds, ctx->stream, P, n, d_coarse, nlist,
+                           d_offsets, d_queries, ld_q, d_rows, ncand, top_k, d_dist, d_ids, ld_out,
+                           ctx->d_diag + 1);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
 }
@@ -425,7 +468,7 @@ int pqh_refine_stream(pqh_ctx_t* ctx, const pqh_tables_t* t1, const pqh_pq_t* pq
                        d_chunk_offsets1, d_chunk_prev1, nullptr};
     const LevelArgs a2{t2, pq2, d_stream2, stream_bytes2, raw_first2, chunk_vectors2,
                        d_chunk_offsets2, d_chunk_prev2, nullptr};
-    return refine(ctx, true, a1, a2, n, cq, d_offsets, d_queries, nq, ld_q, d_rows, ncand, top_k,
+    return refine<false>(ctx, true, a1, a2, n, cq, d_offsets, d_queries, nq, ld_q, d_rows, ncand, top_k,
                   d_dist, d_ids, ld_out);
 }
 
@@ -436,8 +479,39 @@ int pqh_refine_codes(pqh_ctx_t* ctx, const pqh_pq_t* pq1, const void* d_codes1,
                      float* d_dist, long long* d_ids, long long ld_out) {
     const LevelArgs a1{nullptr, pq1, nullptr, 0, 0, 0, nullptr, nullptr, d_codes1};
     const LevelArgs a2{nullptr, pq2, nullptr, 0, 0, 0, nullptr, nullptr, d_codes2};
-    return refine(ctx, false, a1, a2, n, cq, d_offsets, d_queries, nq, ld_q, d_rows, ncand, top_k,
+    return refine<false>(ctx, false, a1, a2, n, cq, d_offsets, d_queries, nq, ld_q, d_rows, ncand, top_k,
                   d_dist, d_ids, ld_out);
+}
+
+int pqh_refine_stream_ip(pqh_ctx_t* ctx, const pqh_tables_t* t1, const pqh_pq_t* pq1,
+                         const unsigned char* d_stream1, unsigned long long stream_bytes1,
+                         int raw_first1, int chunk_vectors1,
+                         const unsigned long long* d_chunk_offsets1, const void* d_chunk_prev1,
+                         const pqh_tables_t* t2, const pqh_pq_t* pq2,
+                         const unsigned char* d_stream2, unsigned long long stream_bytes2,
+                         int raw_first2, int chunk_vectors2,
+                         const unsigned long long* d_chunk_offsets2, const void* d_chunk_prev2,
+                         long long n, const pqh_coarse_t* cq, const long long* d_offsets,
+                         const float* d_queries, long long nq, long long ld_q,
+                         const long long* d_rows, int ncand, int top_k, float* d_dist,
+                         long long* d_ids, long long ld_out) {
+    const LevelArgs a1{t1, pq1, d_stream1, stream_bytes1, raw_first1, chunk_vectors1,
+                       d_chunk_offsets1, d_chunk_prev1, nullptr};
+    const LevelArgs a2{t2, pq2, d_stream2, stream_bytes2, raw_first2, chunk_vectors2,
+                       d_chunk_offsets2, d_chunk_prev2, nullptr};
+    return refine<true>(ctx, true, a1, a2, n, cq, d_offsets, d_queries, nq, ld_q, d_rows, ncand,
+                        top_k, d_dist, d_ids, ld_out);
+}
+
+int pqh_refine_codes_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq1, const void* d_codes1,
+                        const pqh_pq_t* pq2, const void* d_codes2, long long n,
+                        const pqh_coarse_t* cq, const long long* d_offsets, const float* d_queries,
+                        long long nq, long long ld_q, const long long* d_rows, int ncand,
+                        int top_k, float* d_dist, long long* d_ids, long long ld_out) {
+    const LevelArgs a1{nullptr, pq1, nullptr, 0, 0, 0, nullptr, nullptr, d_codes1};
+    const LevelArgs a2{nullptr, pq2, nullptr, 0, 0, 0, nullptr, nullptr, d_codes2};
+    return refine<true>(ctx, false, a1, a2, n, cq, d_offsets, d_queries, nq, ld_q, d_rows, ncand,
+                        top_k, d_dist, d_ids, ld_out);
 }
 
 }  // extern "C"
