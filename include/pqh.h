@@ -1083,6 +1083,61 @@ int pqh_shard_encode_write_parts(pqh_ctx_t* ctx, const pqh_shard_comm_t* comm,
 /* Synchronises; PQH_ERR_REMOTE if some rank's pqh_shard_encode behind d_offsets failed. */
 int pqh_shard_status(pqh_ctx_t* ctx, const unsigned long long* d_offsets);
 
+/* ---- sharded search: several top-k results into one ---------------------------------
+ * pqh_topk_merge: for every query the top_k smallest of all entries of all parts with
+ * id >= 0, each id moved by its part's base, ascending by (dist, moved id), padded with
+ * (+inf, -1) -- the order and the padding of every search here.  d_dist / d_ids are
+ * [parts][nq][k_in], what an all-gather of each rank's (nq, k) result leaves; d_id_base is DEVICE
+ * int64 [parts], or NULL for zeros.  No order is assumed inside a part and padding may sit
+ * anywhere; an entry with id < 0 is ignored whatever its distance; moved ids may exceed 2^32.
+ * What NaN or +inf distances with id >= 0 give is unspecified, but nothing is read or written
+ * out of bounds.  Async on the context's stream.  parts >= 1 and k_in >= 1 (no upper limit),
+ * 1 <= top_k <= the context's limit (PQH_SEARCH_MAX_K, or what pqh_ctx_set_search_max_k set),
+ * else PQH_ERR_ARG; nq == 0 launches nothing; nq >= 2^31 is PQH_ERR_UNSUPPORTED.  A NULL
+ * context answers as in the search calls.
+ * The result over the searches of row blocks of one data set: without a re-rank, dist equals
+ * the dist of one index over all rows bit for bit (the same rows get the same codes and tables
+ * and the same lists are probed; the k smallest of a union are the k smallest of its parts' k
+ * smallest), and ids are equal wherever a query's distances are distinct.  Among equal
+ * distances this result is ordered by global id, the single index by (list, id), and at a tie
+ * across position k each part first chose by its own stream order. */
+int pqh_topk_merge(pqh_ctx_t* ctx,
+                   const float* d_dist, const long long* d_ids /* [parts][nq][k_in] */,
+                   int parts, long long nq, int k_in,
+                   const long long* d_id_base /* DEVICE int64 [parts], or NULL = zeros */,
+                   int top_k, float* d_out_dist, long long* d_out_ids /* [nq][top_k] */);
+
+/* Scratch bytes of pqh_shard_search_merge (device, 8-byte aligned): this rank's record, the
+ * world gathered ones and a word.  0 for arguments the call refuses at once. */
+unsigned long long pqh_shard_search_scratch_bytes(int world, long long nq, int k);
+/* The collective of a search over a row-sharded index: every rank passes the (nq, k) result of
+ * its own rows (local ids), the id of its first row (id_base) and the status of its local
+ * search; every rank gets the same merged result, pqh_topk_merge of all ranks' results with
+ * their bases.  ONE comm->all_gather of a record per rank,
+ *     int64 id_base | int64 status | float dist[nq * k] (+ one zero float when nq * k is odd)
+ *     | int64 ids[nq * k]
+ * so that every field is 8-byte aligned in the gathered buffer; the merge reads the records
+ * where the gather left them and the bases from the headers: no host round trip.  Async.
+ * nq and k must be equal on every rank, as with any collective.
+ * Errors: a NULL context answers as in the search calls; PQH_ERR_ARG at once (before the
+ * gather) when comm, nq < 0 or k outside [1, PQH_SEARCH_MAX_K_WIDE] are unusable and
+ * PQH_ERR_UNSUPPORTED for nq >= 2^31 -- arguments every rank shares.  Any other failure of this
+ * rank keeps it in the gather with a non-zero status in its header and is returned here: a
+ * non-zero `status`, k above this context's limit, a null or misaligned pointer (PQH_ERR_ARG),
+ * scratch_bytes below pqh_shard_search_scratch_bytes (PQH_ERR_CAPACITY; the gather then lands
+ * in the context's own scratch).  If any header carries a non-zero status every rank's outputs
+ * are padding and d_state[0] is set, which pqh_shard_search_status reports as PQH_ERR_REMOTE
+ * -- no rank waits in a collective.  A hook that fails returns PQH_ERR_COMM. */
+int pqh_shard_search_merge(pqh_ctx_t* ctx, const pqh_shard_comm_t* comm,
+                           const float* d_dist, const long long* d_ids /* this rank's [nq][k] */,
+                           long long nq, int k, long long id_base, int status,
+                           void* d_scratch, unsigned long long scratch_bytes,
+                           float* d_out_dist, long long* d_out_ids /* [nq][k], the same on every rank */,
+                           long long* d_state /* DEVICE int64[1] */);
+/* Synchronises; PQH_ERR_REMOTE if some rank's part of the pqh_shard_search_merge behind d_state
+ * failed. */
+int pqh_shard_search_status(pqh_ctx_t* ctx, const long long* d_state);
+
 /* Host: (this rank's global bit offset, the global length) from every rank's bit length. */
 int pqh_shard_offsets(const unsigned long long* lengths, int world, int rank,
                       unsigned long long* offset, unsigned long long* total);

@@ -231,6 +231,11 @@ SIGNATURES = [
     ("pqh_shard_encode_write", I, [P, P, P, P, I, I, I, P, P, ULL, I, P, P, P, P, I, P]),
     ("pqh_shard_encode_tables_parts", I, [P, P, P, P, LL, I, I, I, P, P, P, P]),
     ("pqh_shard_encode_write_parts", I, [P, P, P, P, LL, I, I, I, P, P, ULL, I, P, P, P, P, I, P]),
+    # the merge of top-k results, and the sharded search's collective over it
+    ("pqh_topk_merge", I, [P, P, P, I, LL, I, P, I, P, P]),
+    ("pqh_shard_search_scratch_bytes", ULL, [I, LL, I]),
+    ("pqh_shard_search_merge", I, [P, P, P, P, LL, I, LL, I, P, ULL, P, P, P]),
+    ("pqh_shard_search_status", I, [P, P]),
     ("pqh_shard_offsets", I, [P, I, I, P, P]),
     ("pqh_shard_stitch", I, [I, P, P, P, P, ULL]),
     ("pqh_shard_halo_source", I, [P, I, I, P, P]),

@@ -823,6 +823,39 @@ def search_codes(ctx: Context, codes, lut, k: int, id_base: int = 0, out=None, k
     return dist, ids
 
 
+def merge_topk(ctx: Context, dist, ids, k: int = None, id_base=None, out=None):
+    """(dist, ids), each (nq, k): several top-k results into one (pqh_topk_merge).  dist: device
+    float32 (parts, nq, k_in), ids: int64 of the same shape -- e.g. the searches of the row
+    blocks of an index, stacked, or what an all-gather of every rank's result leaves.  Per query
+    the k (default k_in) smallest of all parts' entries with id >= 0, each id moved by its part's
+    id_base (None: zeros, a sequence of ints, or a device int64 tensor (parts,)), ascending by
+    (dist, moved id), padded with (+inf, -1).  Nothing is assumed about the order inside a part,
+    and padding may sit anywhere.  k <= ctx.search_max_k.  Async.
+
+    Over the searches of the row blocks of one data set (no refine=) the distances are those of
+    one index over all rows, bit for bit, and so are the ids wherever a query's distances are
+    distinct; equal distances come in id order here, in (list, id) order from one IVF."""
+    torch = _torch()
+    if dist.dim() != 3 or ids.shape != dist.shape or dist.dtype != torch.float32 or \
+            ids.dtype != torch.int64:
+        raise PqhError(-1, "merge_topk: dist float32 and ids int64, both (parts, nq, k_in)")
+    parts, nq, k_in = dist.shape
+    k = k_in if k is None else int(k)
+    dist, ids = dist.contiguous(), ids.contiguous()
+    if id_base is not None and not torch.is_tensor(id_base):
+        id_base = torch.tensor([int(v) for v in id_base], dtype=torch.int64, device=dist.device)
+    if id_base is not None:
+        if id_base.dtype != torch.int64 or id_base.numel() != parts:
+            raise PqhError(-1, "merge_topk: id_base is int64 with one entry per part")
+        id_base = id_base.to(dist.device).contiguous()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=dist.device),
+               torch.empty((nq, k), dtype=torch.int64, device=dist.device))
+    check(lib().pqh_topk_merge(ctx.ptr, _ptr(dist), _ptr(ids), parts, nq, k_in, _ptr(id_base), k,
+                               _ptr(out[0]), _ptr(out[1])), "pqh_topk_merge")
+    return out
+
+
 def search_ranges(ctx: Context, tables: Tables, enc: Encoded, lut, range_ptr, ranges, k: int,
                   id_base: int = 0, out=None, keep=None):
     """search() of per-query row ranges, the way an inverted file is probed: query q scores

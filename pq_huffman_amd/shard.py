@@ -22,6 +22,10 @@ host pieces -- row ranges (pqh_shard_block), offsets (pqh_shard_offsets), the st
 (pqh_shard_stitch), the ragged halo's source (pqh_shard_halo_source) -- are C functions this
 module calls.  The remaining helpers issue torch.distributed collectives for the bench's
 overlapped schedule (bench.py), which interleaves the same steps across batches and streams.
+
+The search side is at the end of the module: ShardedIVF, an inverted file whose rows are split
+over the ranks, searched with one all-gather of every rank's top-k and one merge on the device
+(pqh_shard_search_merge; include/pqh.h "sharded search").
 """
 from __future__ import annotations
 
@@ -367,6 +371,9 @@ class TorchComm:
     def _all_gather(self, user, send, recv, nbytes, stream):
         import torch
         import torch.distributed as dist
+        if self.world == 1 and not dist.is_initialized():   # one rank and no process group: a copy
+            return self._on_stream(stream, lambda: self._view(recv, nbytes, torch.uint8).copy_(
+                self._view(send, nbytes, torch.uint8)))
         return self._on_stream(stream, lambda: dist.all_gather_into_tensor(
             self._view(recv, nbytes * self.world, torch.uint8),
             self._view(send, nbytes, torch.uint8), group=self.group))
@@ -516,3 +523,186 @@ def scratch_shard_bits(scratch, world: int, m: int):
     rec = (16 + m + 15) // 16 * 16
     off = rec * (world + 2)
     return scratch[off:off + 8].view(__import__("torch").int64)
+
+
+# ---- the sharded search: one inverted file across ranks, one merged top-k ----------------
+#
+# The rows are split over the ranks in contiguous blocks; every rank searches its own block
+# and the (nq, k) results meet in one all-gather, merged on the device (pqh_topk_merge through
+# pqh_shard_search_merge).  Without refine= the merged distances are those of one index over
+# all rows, bit for bit: the same rows get the same codes, the same lists are probed, and the
+# k smallest of a union are the k smallest of its parts' k smallest.  The ids are equal
+# wherever a query's distances are distinct; among equal distances the merged result is
+# ordered by global id (one index: by (list, id)), and at a tie across position k each rank
+# first chooses by its own stream order.
+
+def id_bases(counts: Sequence[int]):
+    """the exclusive sum of the ranks' row counts: rank r's id_base; global id = id_base +
+    local id"""
+    out, total = [], 0
+    for c in counts:
+        out.append(total)
+        total += int(c)
+    return out
+
+
+def keep_slice(keep, id_base: int, n_local: int):
+    """a rank's part of a keep= over the global ids: keep[id_base : id_base + n_local]"""
+    return keep[id_base:id_base + n_local]
+
+
+def local_ids(ids, id_base: int, n_local: int):
+    """of the global ids (int64 tensor) the ones in [id_base, id_base + n_local), as local ids;
+    the others belong to other ranks"""
+    ids = ids.reshape(-1)
+    return ids[(ids >= id_base) & (ids < id_base + n_local)] - id_base
+
+
+def gather_topk(dist, ids, world: int, rank: int, group=None):
+    """The torch-only half of the search protocol: every rank's (nq, k) result stacked,
+    (world, nq, k) each -- the layout codec.merge_topk and pqh_topk_merge take.  CPU tensors
+    over gloo, device tensors over RCCL; nq and k are the same on every rank."""
+    import torch
+    import torch.distributed as tdist
+    if world == 1:
+        return dist.reshape((1,) + tuple(dist.shape)).clone(), ids.reshape((1,) + tuple(ids.shape)).clone()
+    all_d = torch.empty((world,) + tuple(dist.shape), dtype=dist.dtype, device=dist.device)
+    all_i = torch.empty((world,) + tuple(ids.shape), dtype=ids.dtype, device=ids.device)
+    # (flat views: gloo takes the output as the concatenation of the inputs only)
+    tdist.all_gather_into_tensor(all_d.view(-1), dist.contiguous().view(-1), group=group)
+    tdist.all_gather_into_tensor(all_i.view(-1), ids.contiguous().view(-1), group=group)
+    return all_d, all_i
+
+
+def search_merge(ctx, comm: TorchComm, dist, ids, id_base: int, status: int = 0, check=False):
+    """This rank's part of the merged search (pqh_shard_search_merge): dist float32 and ids
+    int64, both (nq, k) on the device, the result of the rank's own rows with LOCAL ids;
+    id_base the global id of its first row; status the (negative) pqh status of a local search
+    that failed, with dist and ids then only giving the shape.  One all-gather of a record per
+    rank and the merge, asynchronous on ctx's stream.  Returns (dist, ids, state): the merged
+    (nq, k) result, the same on every rank, and a (1,) int64 device tensor that is non-zero
+    when some rank's part failed -- every rank's result is then padding.  check=True
+    synchronises and raises on it here (search_status), otherwise the caller does.  A failure
+    of this rank that the caller did not pass in is raised after the collective."""
+    import torch
+    from .capi import PqhError, check as _check
+    nq, k = dist.shape
+    dev = dist.device
+    dist, ids = dist.contiguous(), ids.contiguous()
+    nbytes = int(_lib().pqh_shard_search_scratch_bytes(comm.world, nq, k))
+    if nbytes == 0:
+        raise PqhError(-1, "pqh_shard_search_scratch_bytes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out_d = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    state = torch.empty(1, dtype=torch.int64, device=dev)
+    ptr = (lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None)
+    comm.error = None
+    comm.register(scratch)   # the hook's buffer, for this call only
+    try:
+        rc = _lib().pqh_shard_search_merge(ctx.ptr, ctypes.byref(comm.struct),
+                                           ptr(dist), ptr(ids), nq, k,
+                                           int(id_base), int(status), ptr(scratch), nbytes,
+                                           ptr(out_d), ptr(out_i), ptr(state))
+    finally:
+        comm.clear()
+    if comm.error is not None:
+        raise comm.error
+    if rc != int(status):
+        _check(rc, "pqh_shard_search_merge")
+    if ctx.stream != torch.cuda.current_stream(dev):
+        scratch.record_stream(ctx.stream)   # (asynchronous: keep it until the stream is done)
+    if check:
+        search_status(ctx, state)
+    return out_d, out_i, state
+
+
+def search_status(ctx, state):
+    """Synchronise; raise if any rank's part of the search_merge behind `state` failed
+    (pqh_shard_search_status: PQH_ERR_REMOTE)."""
+    from .capi import check
+    check(_lib().pqh_shard_search_status(ctx.ptr, ctypes.c_void_p(state.data_ptr())),
+          "pqh_shard_search_status")
+
+
+class ShardedIVF:
+    """An inverted file whose rows are split over the ranks in contiguous blocks: `local` is an
+    ordinary codec.IVF over this rank's rows (its own stream and its own Huffman tables),
+    `id_base` the global id of its first row (the exclusive sum of the ranks' row counts),
+    `n_total` the rows of all ranks; global id = id_base + local id.  search() returns on
+    every rank what the merge of all ranks' results is (see above for what that equals).
+
+    With refine=c every rank re-ranks its own c candidates, and the merged answer is the top k
+    of world * c refined candidates: at least as good as one index's answer, not equal to it.
+
+    Not here: add() and compact() (ids would need a global allocator), fetch() and
+    range_search() across ranks, sharding by lists instead of by rows."""
+
+    def __init__(self, ctx, comm: TorchComm, local, id_base: int, n_total: int):
+        self.ctx, self.comm, self.local = ctx, comm, local
+        self.id_base, self.n_total = int(id_base), int(n_total)
+
+    @property
+    def world(self):
+        return self.comm.world
+
+    def _all_counts(self, value: int):
+        import torch.distributed as tdist
+        if self.comm.world == 1:
+            return [int(value)]
+        counts = [None] * self.comm.world
+        tdist.all_gather_object(counts, int(value), group=self.comm.group)
+        return counts
+
+    @classmethod
+    def build(cls, ctx, comm: TorchComm, pq, coarse, x_local, **ivf_build_kw) -> "ShardedIVF":
+        """Every rank passes the same pq and coarse and its own rows x_local (device float32
+        (n_r, d)); the keywords are codec.IVF.build's.  One small host all-gather of the row
+        counts gives id_base.  comm None: one rank, no process group."""
+        from . import codec
+        comm = comm if comm is not None else TorchComm(1, 0)
+        local = codec.IVF.build(ctx, pq, coarse, x_local, **ivf_build_kw)
+        self = cls(ctx, comm, local, 0, 0)
+        counts = self._all_counts(x_local.shape[0])
+        self.id_base, self.n_total = id_bases(counts)[comm.rank], sum(counts)
+        return self
+
+    def search(self, queries, nprobe: int, k: int, **kw):
+        """(dist, ids), each (nq, k), the same on every rank: local.search(queries, nprobe, k,
+        **kw) -- every option of codec.IVF.search -- then search_merge.  Every rank passes the
+        same queries.  keep: a device bool (n_total,) over the GLOBAL ids, of which the rank
+        takes its slice.  One rank: local.search itself, bit for bit.  A local failure is
+        raised after the collective, another rank's as PQH_ERR_REMOTE (this call then waits for
+        the device once)."""
+        import torch
+        from .capi import PqhError
+        keep = kw.pop("keep", None)
+        if keep is not None:
+            if keep.dtype != torch.bool or keep.shape != (self.n_total,):
+                raise PqhError(-1, "ShardedIVF.search: keep is a bool tensor of shape (n_total,)")
+            keep = keep_slice(keep, self.id_base, self.local.n_ids)
+        if self.comm.world == 1:
+            return self.local.search(queries, nprobe, k, keep=keep, **kw)
+        status, failure = 0, None
+        try:
+            d, i = self.local.search(queries, nprobe, k, keep=keep, **kw)
+        except PqhError as e:   # stay in the collective; the others learn of it there
+            status, failure = e.status, e
+            d = torch.empty((queries.shape[0], k), dtype=torch.float32, device=queries.device)
+            i = torch.empty((queries.shape[0], k), dtype=torch.int64, device=queries.device)
+        out_d, out_i, state = search_merge(self.ctx, self.comm, d, i, self.id_base, status)
+        if failure is not None:
+            raise failure
+        search_status(self.ctx, state)
+        return out_d, out_i
+
+    def remove(self, ids) -> None:
+        """take the rows with the GLOBAL ids `ids` (device int64) out of every later search:
+        each rank removes the ones in its block and ignores the rest"""
+        mine = local_ids(ids, self.id_base, self.local.n_ids)
+        if mine.numel():
+            self.local.remove(mine)
+
+    def live_count(self) -> int:
+        """the rows remove() has left, summed over the ranks (a host all-gather)"""
+        return sum(self._all_counts(self.local.live_count()))
