@@ -1,10 +1,11 @@
 // pqh_radius.hip -- range search: every scanned row with dist(q, v) < radius[q], straight from
 // the compressed stream, as many results as there are.
 //
-//  radius_scan     adc_scan's staging and scoring (pqh_search.hip: one lane per chunk, 64 chunks
-//                  per wave and step, the rows staged in the wave's LDS and scored 64 at a time
-//                  against QB tables held in LDS with the query innermost) with a compare where
-//                  the list offer was.  The output's size depends on the data, so the scan runs
+//  radius_scan     the staging and scoring that adc_scan (pqh_search.hip) has, from the same
+//                  source (pqh_scan_dev.h: one lane per chunk, 64 chunks per wave and step, the
+//                  rows staged in the wave's LDS and scored 64 at a time against QB tables held
+//                  in LDS with the query innermost), with a compare where adc_scan offers to its
+//                  lists.  The output's size depends on the data, so the scan runs
 //                  twice over a plan in the caller's memory:
 //                  FILL = 0  counts: per query a wave-uniform running count (the popcount of the
 //                            hit ballot), stored once per (query, group, wave);
@@ -17,7 +18,7 @@
 //                  The forms are adc_scan's but the list-major one: the whole stream with a
 //                  batch of QB tables, RG (per-query CSR ranges, one query per workgroup), RT
 //                  (one table per range, kept per wave), each with FL (the row mask).
-//  radius_plan     adc_plan's step prefix of the ranges (a copy: pqh_search.hip stays as it is).
+//  scan_plan       (pqh_scan_dev.h) the step prefix of the ranges, as the probe search makes it.
 //  radius_offsets  the plan's counts into exclusive int64 prefixes, and lims.
 //
 // What the fill pass skips: a workgroup whose span counted nothing (before its tables), a wave
@@ -25,31 +26,22 @@
 // 64-bit word per share that the count pass leaves in the plan -- every step of a sub-share
 // without a hit.  -DPQH_RADIUS_NO_SKIP compiles the rule out (tools/bench_range_search.py).
 //
-// dist is the scan's: ((lut[0][c_0] + lut[1][c_1]) + ...) in fp32, no contraction.  The step
-// staging block is adc_scan's, duplicated here (DESIGN.md section 4.5.11 lists the follow-up).
+// dist is the scan's: ((lut[0][c_0] + lut[1][c_1]) + ...) in fp32, no contraction.  What is
+// here is what differs from adc_scan: the contiguous shares, the plan and its header, the
+// counts, the hit words, the skip rule and the fill; the mask rule, the step's location, the
+// staging and the scoring are pqh_scan_dev.h's, and so are the launch geometry (scan_geometry)
+// and the way to the template arguments (scan_dispatch).
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
 #include "pqh_internal.h"
-#include "pqh_decode_dev.h"
+#include "pqh_scan_dev.h"
 
 namespace {
 
-constexpr int kScanWavesMax = 16;          // waves per workgroup (threadIdx.y; threadIdx.x = lane)
-constexpr int kLdsBytes = 160 * 1024;
-constexpr int kCodesRowsPerLane = 4;       // SRC = 1: a wave stages 64 * 4 rows per step
-constexpr int kRangeWaves = 4;             // the probe forms: waves per workgroup, and how many
-constexpr int kRangeFill = 4;              // times over their workgroups fill the compute units
-constexpr int kRangeTableWaves = 2;        // the same with a table per range (and per wave)
-constexpr int kPlanWaves = 16;
 constexpr int kHeaderWords = 8;            // the plan's header, in long longs
 constexpr long long kPlanMagic = 0x5051485241444953ll;   // "PQHRADIS"
-
-__device__ __forceinline__ void wave_lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // The plan, in the caller's memory: the header the count pass writes (the geometry it ran
 // with), then nq * shares + 1 entries, shares = groups * waves, entry q * shares + g * waves + w
@@ -84,7 +76,7 @@ struct RadiusArgs {
     const long long* range_ptr; // RG: [nq + 1]
     const long long* ranges;    // [nr][2]: first row, count
     long long nr;
-    const long long* steps_of;  // [nr + 1]: radius_plan's prefix
+    const long long* steps_of;  // [nr + 1]: scan_plan's prefix
     const uint32_t* keep;       // FL
     long long* plan;            // header, then the entries
     PlanHeader geo;             // what this launch runs with
@@ -94,101 +86,25 @@ struct RadiusArgs {
     unsigned long long* err;
 };
 
-// FL: the rows a lane has to decode of its chunk, of which [r_lo, r_hi) are inside the step's
-// rows: up to the last kept one of them, 0 without one (adc_scan's rule, bit for bit).
-__device__ __forceinline__ int kept_rows(const uint32_t* __restrict__ keep, long long chunk_row0,
-                                         long long r_lo, long long r_hi) {
-    if (r_hi <= r_lo) return 0;
-    const long long w_lo = r_lo >> 5, w_hi = (r_hi - 1) >> 5;
-    for (long long w = w_hi; w >= w_lo; --w) {
-        uint32_t v = keep[w];
-        if (w == w_hi) v &= 0xFFFFFFFFu >> (31 - (int)((r_hi - 1) & 31));
-        if (w == w_lo) v &= 0xFFFFFFFFu << (int)(r_lo & 31);
-        if (v) return (int)(w * 32 + (31 - __clz((int)v)) - chunk_row0) + 1;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ bool range_ok(long long first, long long count, long long n) {
-    return first >= 0 && count >= 0 && first <= n && count <= n - first;
-}
-
-// adc_plan: steps_of[r] = the steps of the ranges before r, steps_of[nr] = all of them; a range
-// of count > 0 rows takes ceil(its chunks / L) steps, an empty or a bad one none, and a bad one
-// sets error bit 2.
-__global__ void __launch_bounds__(64 * kPlanWaves)
-radius_plan(const long long* __restrict__ ranges, long long nr, long long n, int C, int L,
-            long long* __restrict__ plan, unsigned long long* __restrict__ err) {
-    __shared__ long long wsum[kPlanWaves];
-    const int lane = threadIdx.x;
-    const int wave = threadIdx.y;
-    long long carry = 0;
-    bool bad = false;
-    for (long long base = 0; base < nr; base += 64 * kPlanWaves) {
-        const long long r = base + wave * 64 + lane;
-        long long s = 0;
-        if (r < nr) {
-            const long long first = ranges[2 * r], count = ranges[2 * r + 1];
-            if (!range_ok(first, count, n))
-                bad = true;
-            else if (count > 0)
-                s = ((first + count - 1) / C - first / C + L) / L;   // ceil(chunks / L)
-        }
-        long long inc = s;   // the wave's inclusive prefix
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long t = __shfl_up(inc, d);
-            inc += lane >= d ? t : 0;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        lds_barrier();
-        long long before = 0, all = 0;
-        for (int w = 0; w < kPlanWaves; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            all += wsum[w];
-        }
-        if (r < nr) plan[r] = carry + before + inc - s;
-        carry += all;
-        lds_barrier();   // (wsum is written again in the next round)
-    }
-    if (wave == 0 && lane == 0) plan[nr] = carry;
-    if (bad) atomicOr(err, 2ull);
-}
-
 // The counts of the plan into exclusive prefixes, in place, entry `total` the sum of all; and
 // lims[q] = entry q * shares.  One workgroup, 1,024 entries a round: the int64 prefix of
-// radius_plan.  (The lims of a round's entries are written in that round: entry q * shares is
-// final once its round is.)
+// scan_plan (block_prefix).  (The lims of a round's entries are written in that round: entry
+// q * shares is final once its round is.)
 __global__ void __launch_bounds__(64 * kPlanWaves)
 radius_offsets(long long* __restrict__ ent, long long total, long long shares, long long nq,
                long long* __restrict__ lims) {
-    __shared__ long long wsum[kPlanWaves];
     const int lane = threadIdx.x;
     const int wave = threadIdx.y;
     long long carry = 0;
     for (long long base = 0; base < total; base += 64 * kPlanWaves) {
         const long long i = base + wave * 64 + lane;
-        const long long s = i < total ? ent[i] : 0;
-        long long inc = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long t = __shfl_up(inc, d);
-            inc += lane >= d ? t : 0;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        lds_barrier();
-        long long before = 0, all = 0;
-        for (int w = 0; w < kPlanWaves; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            all += wsum[w];
-        }
+        long long all;
+        const long long ex = carry + block_prefix(i < total ? ent[i] : 0, &all);
         if (i < total) {
-            const long long ex = carry + before + inc - s;
             ent[i] = ex;
             if (i % shares == 0) lims[i / shares] = ex;
         }
         carry += all;
-        lds_barrier();
     }
     if (wave == 0 && lane == 0) {
         ent[total] = carry;
@@ -252,24 +168,14 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
     }
 
     // [m][k][QB]; RT: the wave's own [m][k], the waves' tables side by side before the stages
-    const int table_bytes = (mk * 4 + 15) & ~15;
-    float* lut_lds = reinterpret_cast<float*>(lds + (RT ? (size_t)wave * table_bytes : 0));
+    float* lut_lds = reinterpret_cast<float*>(lds + (RT ? (size_t)wave * range_table_bytes(mk) : 0));
     const int per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
     unsigned char* stage = reinterpret_cast<unsigned char*>(lds) +
-                           (RT ? (size_t)waves * table_bytes : (size_t)mk * QB * 4) +
+                           (RT ? (size_t)waves * range_table_bytes(mk) : (size_t)mk * QB * 4) +
                            (size_t)wave * per_wave;
     uint32_t* win = reinterpret_cast<uint32_t*>(stage + a.stage_bytes);
 
-    for (int e = wave * 64 + lane; !RT && e < mk; e += waves * 64) {
-        float v[QB];
-#pragma unroll
-        for (int qq = 0; qq < QB; ++qq) v[qq] = q0 + qq < a.nq ? a.lut[(q0 + qq) * mk + e] : 0.f;
-#pragma unroll
-        for (int u = 0; u < QB / 4; ++u)
-            reinterpret_cast<float4*>(lut_lds + (size_t)e * QB)[u] =
-                make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
-        if constexpr (QB == 1) lut_lds[e] = v[0];
-    }
+    if constexpr (!RT) load_batch_tables<QB>(lut_lds, a.lut, q0, a.nq, mk, wave, lane, waves);
     lds_barrier();   // (the only barrier of the workgroup: from here on every wave is on its own)
 
     // a query past nq has a NaN radius: no row is below it
@@ -325,7 +231,6 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
 #endif
 
     const long long chunks = (a.n + C - 1) / C;
-    const unsigned long long nbits = (unsigned long long)a.nwords * 32;
     long long r_loaded = -1;   // RT: the range whose table the wave holds
     long long r_cur = r_lo;    // RG: the range of the wave's last step (its steps ascend)
 #pragma unroll 1
@@ -338,20 +243,8 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
             if (!((hit_mask >> ((g - g_first) / sub)) & 1ull)) continue;
         bool step_hit = false;
         if constexpr (RG) {
-            const long long t = t0 + g;
-            long long e = r_hi;
-            while (e - r_cur > 1) {
-                const long long mid = r_cur + (e - r_cur) / 2;
-                if (a.steps_of[mid] <= t)
-                    r_cur = mid;
-                else
-                    e = mid;
-            }
-            const long long first = a.ranges[2 * r_cur], count = a.ranges[2 * r_cur + 1];
-            j0 = first / C + (t - a.steps_of[r_cur]) * a.L;
-            jn = min((first + count - 1) / C + 1 - j0, (long long)a.L);
-            lo = max(first, j0 * C);
-            hi = min(first + count, (j0 + jn) * C);
+            const RangeStep rs = range_step(r_cur, r_hi, t0 + g, a.steps_of, a.ranges, C, a.L);
+            r_cur = rs.r, j0 = rs.j0, jn = rs.jn, lo = rs.lo, hi = rs.hi;
             if constexpr (FL) {
                 if (lane < jn) fl_cnt = kept_rows(a.keep, (j0 + lane) * C, max(lo, (j0 + lane) * C),
                                                   min(hi, (j0 + lane + 1) * C));
@@ -359,14 +252,7 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
             }
             if constexpr (RT) {
                 if (r_cur != r_loaded) {
-                    const float* src = a.lut + r_cur * mk;
-                    if (!(mk & 3) && !(reinterpret_cast<uintptr_t>(a.lut) & 15u)) {
-                        for (int e = lane; e < mk / 4; e += 64)
-                            reinterpret_cast<float4*>(lut_lds)[e] =
-                                reinterpret_cast<const float4*>(src)[e];
-                    } else {
-                        for (int e = lane; e < mk; e += 64) lut_lds[e] = src[e];
-                    }
+                    load_range_table(lut_lds, a.lut, r_cur, mk, lane);
                     r_loaded = r_cur;
                 }
             }
@@ -378,90 +264,9 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
                                               min(row0 + nrows, (j0 + lane + 1) * C));
             if (!__ballot(fl_cnt > 0)) continue;
         }
-        const int span = RG ? (int)jn : 64;   // the chunks the stream window is staged for
-        unsigned long long dead = 0;   // lanes whose chunk failed
-        if constexpr (SRC == 0) {
-            bool use_win = false;
-            StreamWin sw{0, 0, false};
-            if (a.win_words > 0) {   // (then L = 64: the window is that of 64 chunks)
-                const unsigned long long b_lo = a.chunk_off[j0];
-                const unsigned long long b_hi = j0 + span < chunks ? a.chunk_off[j0 + span] : nbits;
-                if (b_lo <= nbits && b_hi >= b_lo) {
-                    sw = stage_window<4, true>(a.words, a.nwords, a.chunk_off, j0, chunks, win,
-                                               a.win_words, span);
-                    use_win = sw.in_lds;
-                }
-            }
-            wave_lds_sync();
-            bool ok = true;
-            if (lane < jn && (!FL || fl_cnt > 0)) {
-                const long long j = j0 + lane;
-                const unsigned long long off = a.chunk_off[j];
-                const int cnt_rows = FL ? fl_cnt : (int)min((long long)C, (RG ? hi : a.n) - j * C);
-                const bool raw = CTX && j == 0 && a.raw_first;
-                auto walk = [&](auto& br) -> bool {
-                    if constexpr (NW > 0) {
-                        unsigned long long* st =
-                            reinterpret_cast<unsigned long long*>(stage) + (long long)lane * C * NW;
-                        unsigned long long prev[NW];
-#pragma unroll
-                        for (int w = 0; w < NW; ++w) prev[w] = 0;
-                        if (CTX && !raw) {
-#pragma unroll
-                            for (int w = 0; w < NW; ++w)
-                                prev[w] = static_cast<const unsigned long long*>(a.chunk_prev)[j * NW + w];
-                        }
-                        return walk_packed<CTX, NW, 8>(br, a.T, raw, cnt_rows, prev,
-                                                       [&](int s, int w, unsigned long long row) {
-                                                           st[s * NW + w] = row;
-                                                       });
-                    } else {
-                        unsigned char* st = stage + (long long)lane * C * m;
-                        for (int i = 0; i < m; ++i)
-                            st[i] = (CTX && !raw)
-                                        ? static_cast<const unsigned char*>(a.chunk_prev)[j * m + i]
-                                        : (unsigned char)0;
-                        int cur = 0;
-                        return walk_parts<0>(
-                            br, a.T, m, CTX, raw, cnt_rows,
-                            [&](int i) -> unsigned char& { return st[cur * m + i]; },
-                            [&](int s) {
-                                if (s + 1 < cnt_rows)
-                                    for (int i = 0; i < m; ++i) st[(s + 1) * m + i] = st[s * m + i];
-                                cur = s + 1;
-                            });
-                    }
-                };
-                ok = off <= nbits;   // a start past the stream is refused before anything is read
-                if (ok && use_win) {
-                    const unsigned long long w_bits = (unsigned long long)sw.w_lo * 32;
-                    ok = off >= w_bits && off <= w_bits + (unsigned long long)sw.nw * 32;
-                    if (ok) {
-                        PosRd br;
-                        br.init(win, (uint32_t)(sw.nw + 3), off - w_bits);
-                        ok = walk(br) && w_bits + br.bit() <= nbits;
-                    }
-                } else if (ok) {
-                    SelRd rd;
-                    ok = rd.init(a.words, a.nwords, off);
-                    if (ok) ok = walk(rd.br) && rd.pos() <= nbits;
-                }
-            }
-            dead = __ballot(lane < jn && !ok);
-            if (dead && lane == 0) atomicOr(a.err, 1ull);
-        } else {
-            const long long nbytes = (long long)nrows * m;
-            const unsigned char* src = a.codes + row0 * m;
-            long long done = 0;
-            if (!(reinterpret_cast<uintptr_t>(src) & 3u)) {
-                done = nbytes & ~3ll;
-                for (long long q = lane; q < done / 4; q += 64)
-                    reinterpret_cast<uint32_t*>(stage)[q] =
-                        __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src) + q);
-            }
-            for (long long q = done + lane; q < nbytes; q += 64) stage[q] = src[q];
-        }
-        wave_lds_sync();
+        // lanes whose chunk failed
+        const unsigned long long dead = stage_step<SRC, NW, CTX, FL, RG>(
+            a, stage, win, lane, m, C, j0, jn, hi, row0, nrows, fl_cnt, chunks);
 
         // the stage holds the wave's rows row0 ... row0 + nrows - 1 in order: lane scores
         // rows lane, lane + 64, ..., so a ballot's bits are in row order
@@ -477,6 +282,8 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
                 if (!__ballot(valid)) continue;
             const unsigned char* row = stage + (long long)(r < nrows ? r : 0) * m;
             float sum[QB];
+            // score_row's code, kept here: as a call (five cuts of it were tried) twelve count
+            // instantiations go from 43-73 to 84-99 VGPRs and lose two or three waves a SIMD
             auto add = [&](int i, unsigned c) {
                 // (a failed chunk's slots hold anything: keep the read inside the table)
                 if constexpr (QB == 1) {
@@ -555,70 +362,15 @@ __global__ void __launch_bounds__(64 * kScanWavesMax) radius_scan(const RadiusAr
 }
 
 // ------------------------------------------------------------------- host side
-template <int N>
-using Int = std::integral_constant<int, N>;
-
-int floor_pow2(long long v) {
-    int p = 1;
-    while (2ll * p <= v) p *= 2;
-    return p;
-}
-
-// The launch of both passes, from the shapes alone (pqh_search.hip's scan_launch, with a
-// contiguous share per wave in every form and no lists to exchange at the end).
-struct Geometry {
-    int qb, L, stage_bytes, win_words, waves;
-    long long steps, batches, groups;
-    size_t lds;
-};
-
+// The launch of both passes is scan_geometry's, from the shapes alone: a contiguous share per
+// wave in every form and no lists to exchange at the end, so its LDS is the stage part alone.
 int geometry(const pqh_ctx_t* ctx, int src, int nw, long long n, int m, int k, int C, long long nq,
-             bool rg, bool rt, Geometry* g) {
-    g->qb = rg ? 1 : (m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
-    const long long lut_bytes = (long long)m * k * g->qb * 4;
-    const long long budget = kLdsBytes - lut_bytes;
-    const long long chunks = (n + C - 1) / C;
-    const long long row_bytes = (long long)C * m;
-    g->L = 64;
-    if (((64 * row_bytes + 15) & ~15ll) > budget) g->L = (int)((budget - 16) / row_bytes);
-    if (g->L < 1) return PQH_ERR_UNSUPPORTED;
-    g->stage_bytes = (int)((g->L * row_bytes + 15) & ~15ll);
-    g->win_words = 0;
-    if (src == 0 && g->L == 64) {
-        const long long span_words = (64ll * C * m * 12 + 31) / 32 + 8;
-        const long long ww = std::min<long long>(4096 - 1024 * (nw == 2 ? 1 : 0),
-                                                 std::max<long long>(256, span_words));
-        g->win_words = (int)((ww + 3) & ~3ll);
-        if (g->stage_bytes + (g->win_words + 4) * 4 > budget) g->win_words = 0;
-    }
-    const long long per_wave = g->stage_bytes + (g->win_words ? (g->win_words + 4) * 4 : 0);
-    const long long wave_table = rt ? ((m * k * 4 + 15) & ~15) : 0;
-    if (per_wave + wave_table > kLdsBytes) return PQH_ERR_UNSUPPORTED;
-    int fit = floor_pow2(std::min<long long>(
-        kScanWavesMax, rt ? kLdsBytes / (per_wave + wave_table) : budget / per_wave));
-    g->steps = (chunks + g->L - 1) / g->L;
-    g->batches = (nq + g->qb - 1) / g->qb;
-    long long groups = ctx->tune_search_groups > 0
-                           ? ctx->tune_search_groups
-                           : std::max<long long>(1, ctx->num_cus / g->batches);
-    if (rg) {
-        fit = std::min(fit, rt ? kRangeTableWaves : kRangeWaves);
-        long long wgs = (kRangeFill * (long long)ctx->num_cus + nq - 1) / nq;
-        if (rt) wgs = kLdsBytes / (fit * (per_wave + wave_table)) * (long long)ctx->num_cus / nq;
-        if (ctx->tune_search_groups <= 0)
-            groups = std::min<long long>(wgs, (g->steps + fit - 1) / fit);
-        groups = std::min<long long>(std::max<long long>(groups, 1), 65535);
-    } else {
-        groups = std::min<long long>(std::min<long long>(groups, g->steps), 65535);
-    }
-    g->groups = groups;
-    g->waves = rg ? fit : std::min(fit, floor_pow2((g->steps + 2 * groups - 1) / (2 * groups)));
-    g->lds = rt ? (size_t)g->waves * (size_t)(wave_table + per_wave)
-                : (size_t)lut_bytes + (size_t)g->waves * (size_t)per_wave;
-    return PQH_OK;
+             bool rg, bool rt, ScanGeometry* g) {
+    return scan_geometry(ctx->num_cus, ctx->tune_search_groups, src, nw, n, m, k, C, nq, rg, rt,
+                         false, g);
 }
 
-unsigned long long plan_bytes_of(const Geometry& g, long long nq) {
+unsigned long long plan_bytes_of(const ScanGeometry& g, long long nq) {
     // the header, an entry per (query, group, wave) and the total, a word per (batch, group, wave)
     const unsigned long long shares = (unsigned long long)g.groups * g.waves;
     return ((unsigned long long)kHeaderWords + (unsigned long long)nq * shares + 1 +
@@ -676,7 +428,7 @@ int call_check(pqh_ctx_t* ctx, bool have_src, long long n, const Call& c, bool* 
 
 int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, RadiusArgs a, const Call& c) {
     const bool rg = c.nr >= 0, rt = rg && c.tables_per_range;
-    Geometry g;
+    ScanGeometry g;
     int rc = geometry(ctx, src, nw, a.n, a.m, a.k, a.C, c.nq, rg, rt, &g);
     if (rc) return rc;
     if (c.plan_bytes < plan_bytes_of(g, c.nq)) return PQH_ERR_ARG;
@@ -701,7 +453,7 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, RadiusArgs a, const Ca
         rc = pqh_ensure_ws(ctx, ((size_t)c.nr + 1) * 8);
         if (rc) return rc;
         long long* steps_of = static_cast<long long*>(ctx->ws);
-        hipLaunchKernelGGL(radius_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, c.ranges,
+        hipLaunchKernelGGL(scan_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, c.ranges,
                            c.nr, a.n, a.C, a.L, steps_of, a.err);
         PQH_LAUNCH_CHECK(ctx);
         a.range_ptr = c.range_ptr;
@@ -724,26 +476,11 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, RadiusArgs a, const Ca
         return c.fill ? launch_pass(s, w, cxt, q, tb, fl, std::true_type())
                       : launch_pass(s, w, cxt, q, tb, fl, std::false_type());
     };
-    auto launch = [&](auto s, auto w, auto cxt, auto q, auto tb) -> int {
+    // the range scan's own flags: a.keep set the filtered form, c.fill the pass
+    rc = scan_dispatch(src, nw, cx, g.qb, rg, rt, [&](auto s, auto w, auto cxt, auto q, auto tb) -> int {
         return a.keep ? launch_fl(s, w, cxt, q, tb, std::true_type())
                       : launch_fl(s, w, cxt, q, tb, std::false_type());
-    };
-    auto with_qb = [&](auto s, auto w, auto cxt) -> int {
-        const std::false_type no;
-        if (rt) return launch(s, w, cxt, Int<1>(), std::true_type());
-        if (rg) return launch(s, w, cxt, Int<1>(), no);
-        if constexpr (decltype(w)::value != 2)
-            if (g.qb == 8) return launch(s, w, cxt, Int<8>(), no);
-        return launch(s, w, cxt, Int<4>(), no);
-    };
-    auto with_nw = [&](auto s, auto cxt) -> int {
-        return nw == 1 ? with_qb(s, Int<1>(), cxt) : nw == 2 ? with_qb(s, Int<2>(), cxt)
-                                                             : with_qb(s, Int<0>(), cxt);
-    };
-    if (src == 1)
-        rc = with_nw(Int<1>(), std::false_type());
-    else
-        rc = cx ? with_nw(Int<0>(), std::true_type()) : with_nw(Int<0>(), std::false_type());
+    });
     if (rc) return rc;
     PQH_LAUNCH_CHECK(ctx);
     if (!c.fill) {
@@ -760,44 +497,28 @@ int range_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_s
                  const unsigned long long* d_chunk_offsets, const void* d_chunk_prev,
                  const Call& c) {
     if (!ctx) return pqh_no_ctx_status();
-    if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
-    if (n > 0 && c.nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(d_stream) & 3u) return PQH_ERR_ARG;
-    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
-    if (t->k > 256 || t->m > 16) return PQH_ERR_UNSUPPORTED;
+    RadiusArgs a{};
+    int nw = 0;
+    int rc = stream_source(a, t, d_stream, stream_bytes, n, c.nq, raw_first, chunk_vectors,
+                           d_chunk_offsets, d_chunk_prev, &nw);
+    if (rc) return rc;
     bool run = false;
-    int rc = call_check(ctx, d_stream != nullptr, n, c, &run);
+    rc = call_check(ctx, d_stream != nullptr, n, c, &run);
     if (rc || !run) return rc;
     if (stream_bytes / 4 >= (1ull << 58)) return PQH_ERR_UNSUPPORTED;
-    RadiusArgs a{};
-    a.words = reinterpret_cast<const uint32_t*>(d_stream);
-    a.nwords = (long long)(stream_bytes / 4);
-    a.chunk_off = d_chunk_offsets;
-    a.chunk_prev = d_chunk_prev;
-    a.T = dec_tabs(t, 0);
-    a.raw_first = raw_first;
-    a.n = n;
-    a.m = t->m;
-    a.k = t->k;
-    a.C = chunk_vectors;
-    const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
-    return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, c);
+    return scan_launch(ctx, 0, nw, t->context != 0, a, c);
 }
 
 int range_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k, const Call& c) {
     if (!ctx) return pqh_no_ctx_status();
-    if (m < 1 || k < 1) return PQH_ERR_ARG;
-    if (k > 256 || m > 16) return PQH_ERR_UNSUPPORTED;
-    bool run = false;
-    int rc = call_check(ctx, d_codes != nullptr, n, c, &run);
-    if (rc || !run) return rc;
     RadiusArgs a{};
-    a.codes = static_cast<const unsigned char*>(d_codes);
-    a.n = n;
-    a.m = m;
-    a.k = k;
-    a.C = kCodesRowsPerLane;
-    return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, c);
+    int nw = 0;
+    int rc = codes_source(a, d_codes, n, m, k, &nw);
+    if (rc) return rc;
+    bool run = false;
+    rc = call_check(ctx, d_codes != nullptr, n, c, &run);
+    if (rc || !run) return rc;
+    return scan_launch(ctx, 1, nw, false, a, c);
 }
 
 }  // namespace
@@ -818,7 +539,7 @@ int pqh_range_plan_bytes(pqh_ctx_t* ctx, long long n, int m, int k, int chunk_ve
     // the stream window, and with it the waves that fit, depends on the walk, which the call
     // takes from the alignment of d_chunk_prev: the larger of the two
     for (int nw : {0, (m == 8 || m == 16) ? m / 8 : 0}) {
-        Geometry g;
+        ScanGeometry g;
         int rc = geometry(ctx, src, nw, n, m, k, src ? kCodesRowsPerLane : chunk_vectors, nq,
                           nr >= 0, nr >= 0 && tables_per_range, &g);
         if (rc) return rc;

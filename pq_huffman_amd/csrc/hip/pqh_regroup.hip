@@ -102,6 +102,9 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 //  3. The walk: walk_packed for rows of NW u64 words, walk_parts for any m <= 16, the running
 //     row of the latter being the stage slot that is decoded.  The whole chunk is staged before
 //     anything is stored, so a chunk that fails (error bit 1) leaves its rows unwritten.
+//     (These are the lines of stage_step in pqh_scan_dev.h, here for u16 codes too.  As one
+//     function that both call they cost adc_scan's filtered whole-stream form 2 to 7 %, so the
+//     two copies stay: a change to one is a change to the other.)
 //  4. The write-back: unit U of 8, 4, 2 or 1 bytes, lane q the unit q % per of staged row
 //     q / per (per = units a row), stored at out[dest[row]].
 template <typename CodeT, int NW, bool CTX>

@@ -4,14 +4,18 @@
 //  adc_lut     lut[q][i][c] = ||q_i - cent[i][c]||^2, one thread per entry (the oracle
 //              arithmetic of pqh_pq_assign: fp32, j order, no contraction).
 //  adc_scan    one lane per chunk, 64 chunks per wave and step: the chunks' stream window and
-//              their decoded rows staged in the wave's LDS (walk_packed / walk_parts of
-//              pqh_decode_dev.h), then every row scored against a batch of QB query tables
-//              held in LDS with the query innermost, and offered to QB per-wave top-k lists
-//              (one entry per lane, ascending by (dist, id)), merged per workgroup at the
-//              end.  The codes never reach memory.
+//              their decoded rows staged in the wave's LDS (stage_step; the walks are
+//              pqh_decode_dev.h's), then every row scored against a batch of QB query tables
+//              held in LDS with the query innermost (score_row), and offered to QB per-wave
+//              top-k lists (one entry per lane, ascending by (dist, id)), merged per workgroup
+//              at the end.  The codes never reach memory.  The mask rule, the step prefix of
+//              the ranges (scan_plan), the table loads, a step's location in its range, the
+//              staging and the scoring are pqh_scan_dev.h's, one statement shared with
+//              radius_scan (pqh_radius.hip); here is what differs: the list-major form, the
+//              wave-interleaved step order, the lists, and the exchange and merge at the end.
 //              SRC = 1 loads plain u8 rows into the same stage instead of decoding them.
 //              RG = 1 (the probe search): every query has its own row ranges, so a workgroup
-//              holds one query's table (QB = 1) and its steps are those of adc_plan: a step
+//              holds one query's table (QB = 1) and its steps are those of scan_plan: a step
 //              is up to L chunks of one range, and only the rows inside the range are offered.
 //              RT = 1 (beside RG): one table per range, not per query.  Every wave keeps the
 //              table of its current range in LDS of its own, reloads it when its step's range
@@ -28,7 +32,6 @@
 //              lane.  At most four queries a workgroup (QB <= 4, LM's units with it) and eight
 //              waves: twelve more registers a query, and the waves' lists exchanged through LDS
 //              at the end are waves * QB * 256 * 12 bytes.  KR = 1 is the code it was.
-//  adc_plan    the steps of every range as an exclusive prefix, and the check of its values.
 //  lists_*     the probe list turned round for LM: the pairs of every list in CSR form
 //              (count, scan, fill), cut into work units of up to QB pairs.
 //  adc_merge   one workgroup per query: every scan workgroup's list through the same list code
@@ -42,18 +45,10 @@
 #include <type_traits>
 
 #include "pqh_internal.h"
-#include "pqh_decode_dev.h"
+#include "pqh_scan_dev.h"
 #include "pqh_topk_dev.h"
 
 namespace {
-
-constexpr int kScanWavesMax = 16;          // waves per workgroup (threadIdx.y; threadIdx.x = lane)
-constexpr int kWideWavesMax = 8;           // the same with the wide list (KR = kWideKR)
-constexpr int kLdsBytes = 160 * 1024;
-constexpr int kCodesRowsPerLane = 4;       // SRC = 1: a wave stages 64 * 4 rows per step
-constexpr int kRangeWaves = 4;             // the probe search: waves per workgroup, and how many
-constexpr int kRangeFill = 4;              // times over its workgroups fill the compute units
-constexpr int kRangeTableWaves = 2;        // the same with a table per range (and per wave)
 
 __global__ void __launch_bounds__(256)
 adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
@@ -71,13 +66,6 @@ adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
         acc = acc + t * t;
     }
     lut[idx] = acc;
-}
-
-// LDS written by some lanes of this wave and read by others: all of it done before any lane
-// goes on (the stage and the window are the wave's own, so no workgroup barrier)
-__device__ __forceinline__ void wave_lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
 }
 
 // ------------------------------------------------------------------- the scan
@@ -106,7 +94,7 @@ struct ScanArgs {
     long long* part_id;         // (LM: [nq * nprobe][groups][top_k], per pair and workgroup)
     unsigned long long* err;
     union {
-        // RG: the probe list in CSR form (device data, checked on the device) and adc_plan's
+        // RG: the probe list in CSR form (device data, checked on the device) and scan_plan's
         // prefix
         struct {
             const long long* range_ptr; // [nq + 1]
@@ -126,77 +114,6 @@ struct ScanArgs {
                                 // end: the fields the other forms read stay where they were)
 };
 static_assert(sizeof(ScanArgs) == sizeof(DecTabs) + 176, "FL's field must not move the others");
-
-// FL: the rows a lane has to decode of its chunk, of which [r_lo, r_hi) are inside the step's
-// rows: up to the last kept one of them, 0 without one.  Bits outside [r_lo, r_hi) are masked
-// off, so nothing past row n of the last word counts (r_hi <= n) and no word beyond it is read.
-__device__ __forceinline__ int kept_rows(const uint32_t* __restrict__ keep, long long chunk_row0,
-                                         long long r_lo, long long r_hi) {
-    if (r_hi <= r_lo) return 0;
-    const long long w_lo = r_lo >> 5, w_hi = (r_hi - 1) >> 5;
-    for (long long w = w_hi; w >= w_lo; --w) {
-        uint32_t v = keep[w];
-        if (w == w_hi) v &= 0xFFFFFFFFu >> (31 - (int)((r_hi - 1) & 31));
-        if (w == w_lo) v &= 0xFFFFFFFFu << (int)(r_lo & 31);
-        if (v) return (int)(w * 32 + (31 - __clz((int)v)) - chunk_row0) + 1;
-    }
-    return 0;
-}
-
-// The chunks of a good range: [first / C, (first + count - 1) / C + 1); a range is good when
-// 0 <= first <= n and 0 <= count <= n - first (no sum that could overflow).
-__device__ __forceinline__ bool range_ok(long long first, long long count, long long n) {
-    return first >= 0 && count >= 0 && first <= n && count <= n - first;
-}
-
-// plan[r] = the steps of the ranges before r, plan[nr] = all of them: a range of count > 0
-// rows takes ceil(its chunks / L) steps, an empty or a bad one none (so no step ever leads to
-// it), and a bad one sets error bit 2.  The prefix is over all ranges, not per query: the
-// queries' spans of it may overlap or repeat, and query q's steps are
-// [plan[range_ptr[q]], plan[range_ptr[q + 1]]) whatever the others are.  One workgroup:
-// 1,024 ranges a round, the wave's sums by shuffles, the waves' through LDS.
-constexpr int kPlanWaves = 16;
-__global__ void __launch_bounds__(64 * kPlanWaves)
-adc_plan(const long long* __restrict__ ranges, long long nr, long long n, int C, int L,
-         long long* __restrict__ plan, unsigned long long* __restrict__ err) {
-    __shared__ long long wsum[kPlanWaves];
-    const int lane = threadIdx.x;
-    const int wave = threadIdx.y;
-    long long carry = 0;
-    bool bad = false;
-    for (long long base = 0; base < nr; base += 64 * kPlanWaves) {
-        const long long r = base + wave * 64 + lane;
-        long long s = 0;
-        if (r < nr) {
-            const long long first = ranges[2 * r], count = ranges[2 * r + 1];
-            if (!range_ok(first, count, n))
-                bad = true;
-            else if (count > 0)
-                s = ((first + count - 1) / C - first / C + L) / L;   // ceil(chunks / L)
-        }
-        long long inc = s;   // the wave's inclusive prefix
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long t = __shfl_up(inc, d);
-            inc += lane >= d ? t : 0;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        lds_barrier();
-        long long before = 0, all = 0;
-        for (int w = 0; w < kPlanWaves; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            all += wsum[w];
-        }
-        if (r < nr) plan[r] = carry + before + inc - s;
-        carry += all;
-        lds_barrier();   // (wsum is written again in the next round)
-    }
-    if (wave == 0 && lane == 0) plan[nr] = carry;
-    if (bad) atomicOr(err, 2ull);
-}
-
-// the bytes of one wave's table in the RT form (the stages after the tables stay 16-byte aligned)
-__host__ __device__ __forceinline__ int range_table_bytes(int mk) { return (mk * 4 + 15) & ~15; }
 
 // ------------------------------------------------------------------- the list-major plan
 // The probe list [nq][nprobe] turned round: for every list the pairs q * nprobe + p that probe
@@ -260,7 +177,7 @@ __global__ void __launch_bounds__(256) lists_count(const ListArgs a) {
     if (bad) atomicOr(a.err, 2ull);
 }
 
-// One workgroup, 1,024 lists a round as adc_plan: the exclusive prefixes of the lists' pairs
+// One workgroup, 1,024 lists a round as scan_plan: the exclusive prefixes of the lists' pairs
 // and of their units, cnt[l] left as the first entry of the list's pairs, and every list's
 // units written by its thread.
 __global__ void __launch_bounds__(64 * kPlanWaves) lists_plan(const ListArgs a) {
@@ -366,16 +283,7 @@ adc_scan(const ScanArgs a) {
                     make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
         }
     }
-    for (int e = wave * 64 + lane; !RT && !LM && e < mk; e += waves * 64) {
-        float v[QB];
-#pragma unroll
-        for (int qq = 0; qq < QB; ++qq) v[qq] = q0 + qq < a.nq ? a.lut[(q0 + qq) * mk + e] : 0.f;
-#pragma unroll
-        for (int u = 0; u < QB / 4; ++u)
-            reinterpret_cast<float4*>(lut_lds + (size_t)e * QB)[u] =
-                make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
-        if constexpr (QB == 1) lut_lds[e] = v[0];
-    }
+    if constexpr (!RT && !LM) load_batch_tables<QB>(lut_lds, a.lut, q0, a.nq, mk, wave, lane, waves);
     lds_barrier();
 
     // RG: the query's ranges [r_lo, r_hi) and its steps [t0, t0 + steps) of the plan; range_ptr
@@ -415,7 +323,6 @@ adc_scan(const ScanArgs a) {
     const int kth = a.top_k - 1;
 
     const long long chunks = (a.n + C - 1) / C;
-    const unsigned long long nbits = (unsigned long long)a.nwords * 32;
     // this workgroup's span of steps; its waves take them in turn
     const long long g_lo = (long long)blockIdx.y * steps / gridDim.y;
     const long long g_hi = ((long long)blockIdx.y + 1) * steps / gridDim.y;
@@ -440,39 +347,16 @@ adc_scan(const ScanArgs a) {
         // trip counts differ anyway)
         int fl_cnt = 0;
         if constexpr (RG) {
-            // the step's range: the last one of [r_cur, r_hi) whose steps begin at or before
-            // it (ranges without steps share their successor's entry and are passed over)
-            const long long t = t0 + g;
-            long long e = r_hi;
-            while (e - r_cur > 1) {
-                const long long mid = r_cur + (e - r_cur) / 2;
-                if (a.plan[mid] <= t)
-                    r_cur = mid;
-                else
-                    e = mid;
-            }
-            const long long first = a.ranges[2 * r_cur], count = a.ranges[2 * r_cur + 1];
-            j0 = first / C + (t - a.plan[r_cur]) * a.L;
-            jn = min((first + count - 1) / C + 1 - j0, (long long)a.L);
-            lo = max(first, j0 * C);
-            hi = min(first + count, (j0 + jn) * C);
+            const RangeStep rs = range_step(r_cur, r_hi, t0 + g, a.plan, a.ranges, C, a.L);
+            r_cur = rs.r, j0 = rs.j0, jn = rs.jn, lo = rs.lo, hi = rs.hi;
             if constexpr (FL) {
                 if (lane < jn) fl_cnt = kept_rows(a.keep, (j0 + lane) * C, max(lo, (j0 + lane) * C),
                                                   min(hi, (j0 + lane + 1) * C));
                 if (!__ballot(fl_cnt > 0)) continue;   // (before the table: a step without a kept row)
             }
             if constexpr (RT) {
-                // (the reads of the table before are done: the wave_lds_sync that ends a step;
-                // the new one is complete at the wave_lds_sync before the scoring)
                 if (r_cur != r_loaded) {
-                    const float* src = a.lut + r_cur * mk;
-                    if (!(mk & 3) && !(reinterpret_cast<uintptr_t>(a.lut) & 15u)) {
-                        for (int e = lane; e < mk / 4; e += 64)
-                            reinterpret_cast<float4*>(lut_lds)[e] =
-                                reinterpret_cast<const float4*>(src)[e];
-                    } else {
-                        for (int e = lane; e < mk; e += 64) lut_lds[e] = src[e];
-                    }
+                    load_range_table(lut_lds, a.lut, r_cur, mk, lane);
                     r_loaded = r_cur;
                 }
             }
@@ -491,96 +375,9 @@ adc_scan(const ScanArgs a) {
                                               min(s_hi, (j0 + lane + 1) * C));
             if (!__ballot(fl_cnt > 0)) continue;
         }
-        const int span = RG || LM ? (int)jn : 64;   // the chunks the stream window is staged for
-        unsigned long long dead = 0;   // lanes whose chunk failed
-        if constexpr (SRC == 0) {
-            bool use_win = false;
-            StreamWin sw{0, 0, false};
-            if (a.win_words > 0) {   // (then L = 64: the window is that of 64 chunks)
-                const unsigned long long b_lo = a.chunk_off[j0];
-                const unsigned long long b_hi = j0 + span < chunks ? a.chunk_off[j0 + span] : nbits;
-                // (an index that does not ascend or leaves the stream: no window, every
-                // lane's own offset is then checked by SelRd)
-                if (b_lo <= nbits && b_hi >= b_lo) {
-                    sw = stage_window<4, true>(a.words, a.nwords, a.chunk_off, j0, chunks, win,
-                                               a.win_words, span);
-                    use_win = sw.in_lds;
-                }
-            }
-            wave_lds_sync();
-            bool ok = true;
-            if (lane < jn && (!FL || fl_cnt > 0)) {
-                const long long j = j0 + lane;
-                const unsigned long long off = a.chunk_off[j];
-                // (RG: a chunk cut by the range's end is decoded up to that end only; FL: up to
-                // its last kept row, and one without a kept row is not looked at)
-                const int cnt = FL ? fl_cnt : (int)min((long long)C, (RG || LM ? hi : a.n) - j * C);
-                const bool raw = CTX && j == 0 && a.raw_first;
-                auto walk = [&](auto& br) -> bool {
-                    if constexpr (NW > 0) {
-                        unsigned long long* st =
-                            reinterpret_cast<unsigned long long*>(stage) + (long long)lane * C * NW;
-                        unsigned long long prev[NW];
-#pragma unroll
-                        for (int w = 0; w < NW; ++w) prev[w] = 0;
-                        if (CTX && !raw) {
-#pragma unroll
-                            for (int w = 0; w < NW; ++w)
-                                prev[w] = static_cast<const unsigned long long*>(a.chunk_prev)[j * NW + w];
-                        }
-                        return walk_packed<CTX, NW, 8>(br, a.T, raw, cnt, prev,
-                                                       [&](int s, int w, unsigned long long row) {
-                                                           st[s * NW + w] = row;
-                                                       });
-                    } else {
-                        // the running row is the stage slot being decoded: it starts as a
-                        // copy of the row before it
-                        unsigned char* st = stage + (long long)lane * C * m;
-                        for (int i = 0; i < m; ++i)
-                            st[i] = (CTX && !raw)
-                                        ? static_cast<const unsigned char*>(a.chunk_prev)[j * m + i]
-                                        : (unsigned char)0;
-                        int cur = 0;
-                        return walk_parts<0>(
-                            br, a.T, m, CTX, raw, cnt,
-                            [&](int i) -> unsigned char& { return st[cur * m + i]; },
-                            [&](int s) {
-                                if (s + 1 < cnt)
-                                    for (int i = 0; i < m; ++i) st[(s + 1) * m + i] = st[s * m + i];
-                                cur = s + 1;
-                            });
-                    }
-                };
-                ok = off <= nbits;   // a start past the stream is refused before anything is read
-                if (ok && use_win) {
-                    const unsigned long long w_bits = (unsigned long long)sw.w_lo * 32;
-                    ok = off >= w_bits && off <= w_bits + (unsigned long long)sw.nw * 32;
-                    if (ok) {
-                        PosRd br;
-                        br.init(win, (uint32_t)(sw.nw + 3), off - w_bits);
-                        ok = walk(br) && w_bits + br.bit() <= nbits;
-                    }
-                } else if (ok) {
-                    SelRd rd;
-                    ok = rd.init(a.words, a.nwords, off);
-                    if (ok) ok = walk(rd.br) && rd.pos() <= nbits;
-                }
-            }
-            dead = __ballot(lane < jn && !ok);
-            if (dead && lane == 0) atomicOr(a.err, 1ull);
-        } else {
-            const long long nbytes = (long long)nrows * m;
-            const unsigned char* src = a.codes + row0 * m;
-            long long done = 0;
-            if (!(reinterpret_cast<uintptr_t>(src) & 3u)) {
-                done = nbytes & ~3ll;
-                for (long long q = lane; q < done / 4; q += 64)
-                    reinterpret_cast<uint32_t*>(stage)[q] =
-                        __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src) + q);
-            }
-            for (long long q = done + lane; q < nbytes; q += 64) stage[q] = src[q];
-        }
-        wave_lds_sync();
+        // lanes whose chunk failed
+        const unsigned long long dead = stage_step<SRC, NW, CTX, FL, RG || LM>(
+            a, stage, win, lane, m, C, j0, jn, hi, row0, nrows, fl_cnt, chunks);
 
         // the stage holds the wave's rows row0 ... row0 + nrows - 1 in order: lane scores
         // rows lane, lane + 64, ...
@@ -597,42 +394,7 @@ adc_scan(const ScanArgs a) {
                 if (!__ballot(valid)) continue;
             const unsigned char* row = stage + (long long)(r < nrows ? r : 0) * m;
             float sum[QB];
-            auto add = [&](int i, unsigned c) {
-                // (a failed chunk's slots hold anything: keep the read inside the table)
-                if constexpr (QB == 1) {   // one ds_read_b32 a part
-                    const float v = lut_lds[i * k + (int)min(c, (unsigned)(k - 1))];
-                    if (i == 0)
-                        sum[0] = v;
-                    else
-                        sum[0] = sum[0] + v;
-                }
-                const float4* e = reinterpret_cast<const float4*>(
-                    lut_lds + (size_t)(i * k + (int)min(c, (unsigned)(k - 1))) * QB);
-#pragma unroll
-                for (int u = 0; u < QB / 4; ++u) {
-                    const float4 v = e[u];
-                    if (i == 0) {
-                        sum[4 * u] = v.x, sum[4 * u + 1] = v.y, sum[4 * u + 2] = v.z, sum[4 * u + 3] = v.w;
-                    } else {
-                        sum[4 * u] = sum[4 * u] + v.x;
-                        sum[4 * u + 1] = sum[4 * u + 1] + v.y;
-                        sum[4 * u + 2] = sum[4 * u + 2] + v.z;
-                        sum[4 * u + 3] = sum[4 * u + 3] + v.w;
-                    }
-                }
-            };
-            if constexpr (NW > 0) {
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    const unsigned long long word = reinterpret_cast<const unsigned long long*>(row)[w];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) add(w * 8 + i, (unsigned)(word >> (8 * i)) & 255u);
-                }
-            } else {
-                add(0, row[0]);
-#pragma unroll 1
-                for (int i = 1; i < m; ++i) add(i, row[i]);
-            }
+            score_row<NW>(row, lut_lds, m, k, sum);
             const long long id = row0 + r;
 #pragma unroll
             for (int qq = 0; qq < QB; ++qq)
@@ -826,15 +588,6 @@ adc_merge_wide(const float* __restrict__ part_d, const long long* __restrict__ p
     }
 }
 // ------------------------------------------------------------------- host side
-template <int N>
-using Int = std::integral_constant<int, N>;
-
-int floor_pow2(long long v) {
-    int p = 1;
-    while (2ll * p <= v) p *= 2;
-    return p;
-}
-
 int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long long lists,
                  long long nq, int top_k, long long id_base, float* d_dist, long long* d_ids) {
     hipLaunchKernelGGL(top_k > PQH_SEARCH_MAX_K ? adc_merge_wide : adc_merge, dim3((unsigned)nq),
@@ -864,80 +617,36 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
                 float* d_dist, long long* d_ids, bool rg = false, bool rt = false,
                 const ListProbe* ls = nullptr) {
     if (a.nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
-    const int m = a.m, k = a.k;
-    // the batch's tables: at most 64 KB; 16-part rows keep to four queries (eight running
-    // sums beside sixteen unrolled parts spill registers)
-    // top_k > 64, the wide list: four queries at the most (its entries are registers) and
-    // kWideWavesMax waves (the lists' exchange at the end has to fit the LDS)
+    // the stage, the window, the batch and the grid of the whole-stream and the probe forms
+    // (scan_geometry); top_k > 64 is the wide list
     const bool wide = a.top_k > PQH_SEARCH_MAX_K;
-    const int qb = rg ? 1 : (!wide && m <= 8 && (long long)m * k <= 2048) ? 8 : 4;
-    const long long lut_bytes = (long long)m * k * qb * 4;
-    const long long budget = kLdsBytes - lut_bytes;
-    const long long chunks = (a.n + a.C - 1) / a.C;
-    // a wave's stage: the rows of 64 chunks, or of as many as fit
-    const long long row_bytes = (long long)a.C * m;
-    a.L = 64;
-    if (((64 * row_bytes + 15) & ~15ll) > budget) a.L = (int)((budget - 16) / row_bytes);
-    if (a.L < 1) return PQH_ERR_UNSUPPORTED;   // (a chunk of more than ~96 KB of codes)
-    a.stage_bytes = (int)((a.L * row_bytes + 15) & ~15ll);
-    // the stream window as pqh_decode's row kernels size it (a longer span is read from
-    // global memory)
-    a.win_words = 0;
-    if (src == 0 && a.L == 64) {
-        const long long span_words = (64ll * a.C * m * 12 + 31) / 32 + 8;
-        const long long ww = std::min<long long>(4096 - 1024 * (nw == 2 ? 1 : 0),
-                                                 std::max<long long>(256, span_words));
-        a.win_words = (int)((ww + 3) & ~3ll);
-        if (a.stage_bytes + (a.win_words + 4) * 4 > budget) a.win_words = 0;
-    }
-    const long long per_wave = a.stage_bytes + (a.win_words ? (a.win_words + 4) * 4 : 0);
-    // rt: every wave has a table of its own beside its stage (one of them is in the budget,
-    // so one wave always fits)
-    const long long wave_table = rt ? range_table_bytes(m * k) : 0;
-    if (per_wave + wave_table > kLdsBytes) return PQH_ERR_UNSUPPORTED;   // (rounding, at most)
-    int fit = floor_pow2(std::min<long long>(
-        wide ? kWideWavesMax : kScanWavesMax, rt ? kLdsBytes / (per_wave + wave_table) : budget / per_wave));
-    a.steps = (chunks + a.L - 1) / a.L;
+    ScanGeometry g;
+    int rc = scan_geometry(ctx->num_cus, ctx->tune_search_groups, src, nw, a.n, a.m, a.k, a.C, a.nq,
+                           rg, rt, wide, &g);
+    if (rc) return rc;
+    const int qb = g.qb;
+    a.L = g.L;
+    a.stage_bytes = g.stage_bytes;
+    a.win_words = g.win_words;
+    a.steps = g.steps;
+    long long batches = g.batches, groups = g.groups;
+    int waves = g.waves;
     // ls: the units are device data, at most one per pair and at most one part-filled per list
     const long long npairs = ls ? a.nq * ls->nprobe : 0;
-    const long long batches =
-        ls ? std::min<long long>(npairs, ls->nlist + npairs / qb) : (a.nq + qb - 1) / qb;
-    // one workgroup per compute unit over all query batches (a workgroup's tables take most
-    // of a compute unit's LDS), each wave with at least two steps where there are that many
-    long long groups = ctx->tune_search_groups > 0 ? ctx->tune_search_groups
-                                                   : std::max<long long>(1, ctx->num_cus / batches);
-    if (rg) {
-        // A query's steps are known on the device only: the grid is fixed here.  One table
-        // leaves room for several workgroups of kRangeWaves waves on a compute unit, and
-        // nq * groups workgroups fill the compute units kRangeFill times over; a query has at
-        // most the stream's steps unless its ranges overlap.
-        fit = std::min(fit, rt ? kRangeTableWaves : kRangeWaves);
-        // rt: the waves' tables are most of the LDS, which holds twelve waves a compute unit at
-        // m = 8 where the one-table form holds twenty.  The grid is what is resident at once
-        // and no more (rounded down: a workgroup more would wait for a whole round of the
-        // others), in workgroups of two waves so that the rounding costs little
-        long long wgs = (kRangeFill * (long long)ctx->num_cus + a.nq - 1) / a.nq;
-        if (rt)
-            wgs = kLdsBytes / (fit * (per_wave + wave_table)) * (long long)ctx->num_cus / a.nq;
-        if (ctx->tune_search_groups <= 0)
-            groups = std::min<long long>(wgs, (a.steps + fit - 1) / fit);
-        groups = std::min<long long>(std::max<long long>(groups, 1), 65535);
-    } else if (ls) {
+    if (ls) {
+        batches = std::min<long long>(npairs, ls->nlist + npairs / qb);
         // the default fills the compute units with the bound's units (a workgroup's tables
         // take most of a compute unit's LDS) and no list has more steps than the stream; a
         // group without steps writes the padding
+        groups = ctx->tune_search_groups > 0 ? ctx->tune_search_groups
+                                             : std::max<long long>(1, ctx->num_cus / batches);
         if (ctx->tune_search_groups <= 0) groups = std::min<long long>(groups, a.steps);
         groups = std::min<long long>(groups, 65535);
-    } else {
-        groups = std::min<long long>(std::min<long long>(groups, a.steps), 65535);
+        // a list's steps are known on the device only; twice the mean list's share of steps
+        // per group, kListWaves at the most
+        const long long mean2 = 2 * ((a.steps + ls->nlist - 1) / ls->nlist);
+        waves = std::min(std::min(g.fit, kListWaves), floor_pow2((mean2 + groups - 1) / groups));
     }
-    // ls: a list's steps are known on the device only; twice the mean list's share of steps
-    // per group, kListWaves at the most
-    const long long mean2 = ls ? 2 * ((a.steps + ls->nlist - 1) / ls->nlist) : 0;
-    const int waves =
-        rg   ? fit
-        : ls ? std::min(std::min(fit, kListWaves), floor_pow2((mean2 + groups - 1) / groups))
-             : std::min(fit, floor_pow2((a.steps + 2 * groups - 1) / (2 * groups)));
     // (a workgroup merges its waves' lists; ls: a list per pair and group)
     const long long lists = ls ? ls->nprobe * groups : groups;
     const size_t entries = (size_t)a.nq * lists * a.top_k;
@@ -947,14 +656,14 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
     const size_t plan_bytes = rg   ? ((size_t)a.nr + 1) * 8
                               : ls ? ((size_t)batches * 3 + 1) * 8 + cnt_bytes + (size_t)npairs * 4
                                    : 0;
-    int rc = pqh_ensure_ws(ctx, entries * 12 + 16 + plan_bytes);
+    rc = pqh_ensure_ws(ctx, entries * 12 + 16 + plan_bytes);
     if (rc) return rc;
     a.part_id = static_cast<long long*>(ctx->ws);
     a.part_d = reinterpret_cast<float*>(a.part_id + entries);
     a.err = ctx->d_diag + 1;
     if (rg) {
         long long* plan = static_cast<long long*>(ctx->ws) + ((entries * 12 + 15) / 8);
-        hipLaunchKernelGGL(adc_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, a.ranges, a.nr,
+        hipLaunchKernelGGL(scan_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, a.ranges, a.nr,
                            a.n, a.C, a.L, plan, a.err);
         PQH_LAUNCH_CHECK(ctx);
         a.plan = plan;
@@ -987,10 +696,8 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         a.pairs = la.pairs;
     }
     // (the end of the kernel exchanges the waves' lists, 12 bytes an entry, through the same LDS)
-    const size_t lds = std::max<size_t>(
-        rt ? (size_t)waves * (size_t)(wave_table + per_wave)
-           : (size_t)lut_bytes + (size_t)waves * (size_t)per_wave,
-        (size_t)waves * qb * (wide ? kWideKR : 1) * 64 * 12);
+    const size_t lds =
+        std::max<size_t>(g.lds_of(waves), (size_t)waves * qb * (wide ? kWideKR : 1) * 64 * 12);
     auto launch_fl = [&](auto s, auto w, auto c, auto q, auto tb, auto lm, auto fl) -> int {
         auto go = [&](auto* fn) -> int {
             if (lds > 64 * 1024)
@@ -1009,32 +716,17 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
                            decltype(q)::value, decltype(q)::value == 1, decltype(tb)::value,
                            decltype(lm)::value, decltype(fl)::value>);
     };
-    // a.keep set (the *_masked calls): the filtered form of the same kernel
     auto launch = [&](auto s, auto w, auto c, auto q, auto tb, auto lm) -> int {
         return a.keep ? launch_fl(s, w, c, q, tb, lm, std::true_type())
                       : launch_fl(s, w, c, q, tb, lm, std::false_type());
     };
-    auto with_qb = [&](auto s, auto w, auto c) -> int {
-        const std::false_type no;
-        if (rt) return launch(s, w, c, Int<1>(), std::true_type(), no);
-        if (rg) return launch(s, w, c, Int<1>(), no, no);
-        if (ls) {
-            if constexpr (decltype(w)::value != 2)
-                if (qb == 8) return launch(s, w, c, Int<8>(), no, std::true_type());
-            return launch(s, w, c, Int<4>(), no, std::true_type());
-        }
-        if constexpr (decltype(w)::value != 2)
-            if (qb == 8) return launch(s, w, c, Int<8>(), no, no);
-        return launch(s, w, c, Int<4>(), no, no);
-    };
-    auto with_nw = [&](auto s, auto c) -> int {
-        return nw == 1 ? with_qb(s, Int<1>(), c) : nw == 2 ? with_qb(s, Int<2>(), c)
-                                                           : with_qb(s, Int<0>(), c);
-    };
-    if (src == 1)
-        rc = with_nw(Int<1>(), std::false_type());
-    else
-        rc = cx ? with_nw(Int<0>(), std::true_type()) : with_nw(Int<0>(), std::false_type());
+    // search's own flags: LM for the batch forms of a *_lists call, a.keep set (the *_masked
+    // calls) the filtered form of the same kernel, and the wide list
+    rc = scan_dispatch(src, nw, cx, qb, rg, rt, [&](auto s, auto w, auto c, auto q, auto tb) -> int {
+        if constexpr (decltype(q)::value > 1)
+            if (ls) return launch(s, w, c, q, tb, std::true_type());
+        return launch(s, w, c, q, tb, std::false_type());
+    });
     if (rc) return rc;
     PQH_LAUNCH_CHECK(ctx);
     return merge_launch(ctx, a.part_d, a.part_id, lists, a.nq, a.top_k, id_base, d_dist, d_ids);
@@ -1055,7 +747,7 @@ int search_check(pqh_ctx_t* ctx, bool have_src, long long n, const float* d_lut,
     return PQH_OK;
 }
 
-// the probe list's host-side checks (its values are device data: adc_plan and adc_scan)
+// the probe list's host-side checks (its values are device data: scan_plan and adc_scan)
 bool ranges_args_ok(long long nq, const long long* d_range_ptr, const long long* d_ranges,
                     long long nr) {
     return nr >= 0 && !(nq > 0 && (!d_range_ptr || (nr > 0 && !d_ranges)));
@@ -1087,40 +779,28 @@ int search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_
                   float* d_dist, long long* d_ids, const ListProbe* ls = nullptr,
                   const unsigned int* d_keep = nullptr) {
     if (!ctx) return pqh_no_ctx_status();
-    if (!t || chunk_vectors < 1) return PQH_ERR_ARG;
-    if (n > 0 && nq > 0 && (stream_bytes < 4 || !d_chunk_offsets)) return PQH_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_stream) | reinterpret_cast<uintptr_t>(d_keep)) & 3u)
-        return PQH_ERR_ARG;
-    if (t->context && !d_chunk_prev && (!raw_first || n > chunk_vectors)) return PQH_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_keep) & 3u) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
     if (ls && !lists_args_ok(nq, ls)) return PQH_ERR_ARG;
-    if (t->k > 256 || t->m > 16 || (ls && lists_too_many(nq, ls))) return PQH_ERR_UNSUPPORTED;
+    ScanArgs a{};
+    int nw = 0;
+    int rc = stream_source(a, t, d_stream, stream_bytes, n, nq, raw_first, chunk_vectors,
+                           d_chunk_offsets, d_chunk_prev, &nw);
+    if (rc) return rc;
+    if (ls && lists_too_many(nq, ls)) return PQH_ERR_UNSUPPORTED;
     bool run = false;
-    int rc = search_check(ctx, d_stream != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
+    rc = search_check(ctx, d_stream != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
     if (rc || !run) return rc;
     if (pr && pr->nr == 0)
         return merge_launch(ctx, nullptr, nullptr, 0, nq, top_k, id_base, d_dist, d_ids);
     if (stream_bytes / 4 >= (1ull << 58)) return PQH_ERR_UNSUPPORTED;
-    ScanArgs a{};
-    a.words = reinterpret_cast<const uint32_t*>(d_stream);
-    a.nwords = (long long)(stream_bytes / 4);
-    a.chunk_off = d_chunk_offsets;
-    a.chunk_prev = d_chunk_prev;
-    a.T = dec_tabs(t, 0);
-    a.raw_first = raw_first;
-    a.n = n;
-    a.m = t->m;
-    a.k = t->k;
-    a.C = chunk_vectors;
     a.lut = d_lut;
     a.nq = nq;
     a.top_k = top_k;
     a.keep = d_keep;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
     if (ls) a.offsets = ls->offsets, a.nprobe = ls->nprobe, a.pair_tables = ls->tables;
-    // rows of whole u64 words with the chunk contexts readable as such: the packed walk
-    const bool packed = (t->m == 8 || t->m == 16) && !(reinterpret_cast<uintptr_t>(d_chunk_prev) & 7);
-    return scan_launch(ctx, 0, packed ? t->m / 8 : 0, t->context != 0, a, id_base, d_dist, d_ids,
+    return scan_launch(ctx, 0, nw, t->context != 0, a, id_base, d_dist, d_ids,
                        pr != nullptr, pr && pr->tables, ls);
 }
 
@@ -1131,28 +811,26 @@ int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                  float* d_dist, long long* d_ids, const ListProbe* ls = nullptr,
                  const unsigned int* d_keep = nullptr) {
     if (!ctx) return pqh_no_ctx_status();
-    if (m < 1 || k < 1 || (reinterpret_cast<uintptr_t>(d_keep) & 3u)) return PQH_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_keep) & 3u) return PQH_ERR_ARG;
     if (pr && !ranges_args_ok(nq, pr->range_ptr, pr->ranges, pr->nr)) return PQH_ERR_ARG;
     if (ls && !lists_args_ok(nq, ls)) return PQH_ERR_ARG;
-    if (k > 256 || m > 16 || (ls && lists_too_many(nq, ls))) return PQH_ERR_UNSUPPORTED;
+    ScanArgs a{};
+    int nw = 0;
+    int rc = codes_source(a, d_codes, n, m, k, &nw);
+    if (rc) return rc;
+    if (ls && lists_too_many(nq, ls)) return PQH_ERR_UNSUPPORTED;
     bool run = false;
-    int rc = search_check(ctx, d_codes != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
+    rc = search_check(ctx, d_codes != nullptr, n, d_lut, nq, top_k, id_base, d_dist, d_ids, &run);
     if (rc || !run) return rc;
     if (pr && pr->nr == 0)
         return merge_launch(ctx, nullptr, nullptr, 0, nq, top_k, id_base, d_dist, d_ids);
-    ScanArgs a{};
-    a.codes = static_cast<const unsigned char*>(d_codes);
-    a.n = n;
-    a.m = m;
-    a.k = k;
-    a.C = kCodesRowsPerLane;
     a.lut = d_lut;
     a.nq = nq;
     a.top_k = top_k;
     a.keep = d_keep;
     if (pr) a.range_ptr = pr->range_ptr, a.ranges = pr->ranges, a.nr = pr->nr;
     if (ls) a.offsets = ls->offsets, a.nprobe = ls->nprobe, a.pair_tables = ls->tables;
-    return scan_launch(ctx, 1, (m == 8 || m == 16) ? m / 8 : 0, false, a, id_base, d_dist, d_ids,
+    return scan_launch(ctx, 1, nw, false, a, id_base, d_dist, d_ids,
                        pr != nullptr, pr && pr->tables, ls);
 }
 

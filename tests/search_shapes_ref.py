@@ -14,7 +14,7 @@ import ivf_ref
 import ivf_residual_ref as ref
 import search_lists_ref as lref
 
-ROUND = 1024          # the ranges (adc_plan) or lists (lists_plan) of one round of a plan kernel
+ROUND = 1024          # the ranges (scan_plan) or lists (lists_plan) of one round of a plan kernel
 LANES = 64            # a step is up to 64 chunks; an offer is 64 candidates, one per lane
 SERIAL_MAX = 6        # list_offer: up to six passing lanes are inserted one by one
 
@@ -141,7 +141,7 @@ def prefix(counts, carry=True):
 
 
 def range_steps(ranges, n, C, L=LANES):
-    """adc_plan's steps of every range: ceil(its chunks / L), none for an empty or a bad one"""
+    """scan_plan's steps of every range: ceil(its chunks / L), none for an empty or a bad one"""
     f, c = ranges[:, 0], ranges[:, 1]
     good = (f >= 0) & (c > 0) & (f <= n) & (c <= n - f)
     last = np.where(good, f + c - 1, 0)

@@ -9,7 +9,7 @@ the byte-wise walk; QB = 1 for the range forms, else 8 if m <= 8 and m * K <= 20
 
   path                                          reached by                             test
   --------------------------------------------  -------------------------------------  ----------------------------
-  adc_plan, second and later rounds (carry,     nr = 1,025 (two rounds, the second of  test_ranges_plan_rounds
+  scan_plan, second and later rounds (carry,    nr = 1,025 (two rounds, the second of  test_ranges_plan_rounds
   wsum written again after the closing          one range) and 2,111 (three); 1,024 is
   barrier)                                      exactly one
   lists_plan, the same (carry_p, carry_u,       nlist = 1,025 and 2,111, hot lists of  test_lists_plan_rounds,
@@ -252,7 +252,7 @@ def test_codes_at_byte_one(gpu, m, K):
 @pytest.mark.parametrize("form", ["query", "range"])
 @pytest.mark.parametrize("nr", [1024, 1025, 2111])
 def test_ranges_plan_rounds(gpu, nr, form):
-    """adc_plan over one round exactly, one range more, and three rounds: a table per query on
+    """scan_plan over one round exactly, one range more, and three rounds: a table per query on
     a K = 256 context stream, a table per range at K = 16.  Then the same ranges with
     out-of-bounds ones in every round: skipped, reported, every other range as it was."""
     torch, codec, ctx = gpu
