@@ -749,6 +749,50 @@ int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep /* [n], nonzero = 
  * pqh_decode_status). */
 int pqh_ivf_status(pqh_ctx_t* ctx);
 
+/* ---- rotated index: a linear map in front of the quantizers (OPQ) ------------------------
+ * A d x d matrix R applied to every row before the coarse quantizer and the PQ see it, and the
+ * two sums the training of such a matrix needs (codec.opq_train).  Any matrix is accepted: the
+ * library applies a linear map, that it is orthonormal is the caller's property
+ * (codec.Rotation.defect).
+ * Argument checks need no device and come first in these calls; a NULL context is answered next
+ * (PQH_ERR_NO_DEVICE when no HIP device is visible, else PQH_ERR_ARG).
+ * 1 <= d <= PQH_ROT_MAX_D, no multiple of anything required; beyond it PQH_ERR_UNSUPPORTED. */
+typedef struct pqh_rotation pqh_rotation_t;
+#define PQH_ROT_MAX_D 1024
+
+/* R: HOST [d][d] fp32.  The device keeps R and its transpose (8 * d * d bytes), as
+ * pqh_coarse_create keeps two copies; synchronous.  PQH_ERR_ARG: a null pointer, d < 1. */
+int pqh_rotation_create(pqh_ctx_t* ctx, const float* R /* HOST [d][d] */, int d,
+                        pqh_rotation_t** rot);
+/* Synchronises the stream of the context it was made with, which must still exist. */
+int pqh_rotation_destroy(pqh_rotation_t* rot);
+
+/* d_out[v][j] = sum_t x[v][t] * R[t][j]; transpose = 1: R[j][t] in place of R[t][j].  Each
+ * output is one fp32 chain from +0.0 with t ascending, one multiply and one add per element, no
+ * contraction -- the arithmetic of pqh_coarse_assign, so float32 array operations of numpy give
+ * the same bits.  Rows of x are ld_x >= d floats apart and rows of d_out ld_out >= d; the floats
+ * between rows of x are never read, those between rows of d_out never written.  d_out must not
+ * overlap x.  The bits do not depend on the grid.  n == 0 launches nothing.  Asynchronous on the
+ * context's stream.  PQH_ERR_ARG: a null pointer (d_x and d_out may be NULL when n == 0), n < 0,
+ * ld_x < d, ld_out < d, transpose not 0 or 1. */
+int pqh_rotate(pqh_ctx_t* ctx, const pqh_rotation_t* rot, const float* d_x, long long n,
+               long long ld_x, float* d_out, long long ld_out, int transpose);
+
+/* moments[a][b] = sum_v x[v][a] * y[v][b], deterministic and exact in the way
+ * pqh_kmeans_train's sums are: each product is one fp32 multiply p, f = rn(p * 2^s) is an int64
+ * (__double2ll_rn(ldexp((double)p, s))), the f are added as integers -- so neither the order nor
+ * the grid can matter -- and moments[a][b] = ldexp((double)sum, -s).
+ * s = 61 - ceil(log2(max|x| * max|y| * n)) with the product in double, clamped to [-126, 100],
+ * 40 when the product is 0: pqh_kmeans_train's exponent with max|x| * max|y| for max|x|.
+ * x [n][dx] and y [n][dy] are device rows ld_x >= dx and ld_y >= dy floats apart (x and y may be
+ * the same buffer); moments is HOST [dx][dy].  1 <= dx, dy <= PQH_ROT_MAX_D, else
+ * PQH_ERR_UNSUPPORTED.  n == 0 gives zeros.  Synchronous, as pqh_kmeans_train is.
+ * PQH_ERR_ARG: a null pointer (d_x and d_y may be NULL when n == 0), n < 0, dx or dy < 1,
+ * ld_x < dx, ld_y < dy. */
+int pqh_cross_moments(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int dx,
+                      const float* d_y, long long ld_y, int dy,
+                      double* moments /* HOST [dx][dy] */);
+
 /* ---- inner-product search: the metric around the scan -----------------------------------
  * The scans order plain fp32 sums with `<`, so a maximum-inner-product search scores a pair with
  * the NEGATED inner product: smaller is nearer, results are ordered by (score, id) ascending

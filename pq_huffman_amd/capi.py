@@ -163,6 +163,10 @@ SIGNATURES = [
     ("pqh_ivf_layout", I, [P, P, LL, I, P, P]),
     ("pqh_coarse_probe", I, [P, P, P, LL, LL, I, P, P, P, P, P]),
     ("pqh_ivf_status", I, [P]),
+    # the rotation in front of the quantizers, and the sums its training needs
+    ("pqh_rotation_create", I, [P, P, I, P]), ("pqh_rotation_destroy", I, [P]),
+    ("pqh_rotate", I, [P, P, P, LL, LL, P, LL, I]),
+    ("pqh_cross_moments", I, [P, P, LL, LL, I, P, LL, I, P]),
     ("pqh_ivf_residuals", I, [P, P, P, LL, LL, P, P, P, LL]),
     ("pqh_adc_tables_residual", I, [P, P, P, P, LL, LL, P, I, P]),
     ("pqh_search_stream_range_tables", I,

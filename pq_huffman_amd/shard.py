@@ -657,8 +657,9 @@ class ShardedIVF:
     @classmethod
     def build(cls, ctx, comm: TorchComm, pq, coarse, x_local, **ivf_build_kw) -> "ShardedIVF":
         """Every rank passes the same pq and coarse and its own rows x_local (device float32
-        (n_r, d)); the keywords are codec.IVF.build's.  One small host all-gather of the row
-        counts gives id_base.  comm None: one rank, no process group."""
+        (n_r, d)); the keywords are codec.IVF.build's, rotation= among them: every rank must
+        then be given the same R, as it is the same pq and coarse.  One small host all-gather of
+        the row counts gives id_base.  comm None: one rank, no process group."""
         from . import codec
         comm = comm if comm is not None else TorchComm(1, 0)
         local = codec.IVF.build(ctx, pq, coarse, x_local, **ivf_build_kw)
