@@ -94,8 +94,6 @@ int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_c
 // a coarse quantizer's shape and its device centroids [nlist][d] (pqh_ivf.hip), for the re-rank
 // of a residual index (pqh_refine.hip); PQH_ERR_ARG for a null quantizer
 int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_cent);
-// its transposed copy [d][nlist], which the probe kernels read (pqh_metric.hip)
-int pqh_coarse_view_t(const pqh_coarse_t* cq, const float** d_cent_t);
 // pqh_shard_encode's histogram / size / write with this shard's raw-first flag in device
 // memory (1: row 0 raw, no halo pair; 0: row 0 in the context of d_prev_row) -- pqh_huff.hip
 extern "C" {

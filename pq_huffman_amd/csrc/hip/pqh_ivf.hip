@@ -1,8 +1,17 @@
 // pqh_ivf.hip -- the inverted-file front end of the probe search (pqh_search_*_ranges): a coarse
 // quantizer over full vectors, the list layout, and the probe list of every query.
 //
-//  coarse_assign  list[v] = argmin_l ||x[v] - c[l]||^2, the exact direct form (subtract,
-//                 multiply, add per element, j ascending, no contraction).  A workgroup of 256
+// Two metrics, the template parameter IP of the kernels that sum (the host picks the
+// instantiation; an `if constexpr` stands around the lines of the sum and nowhere else):
+//   L2  dist(x, y) = acc,  acc = +0.0f;  for j ascending:  t = x[j] - y[j];  acc = acc + t * t
+//   IP  nip(x, y)  = acc,  acc = +0.0f;  for j ascending:  acc = acc - x[j] * y[j]
+// The scan, the top-k lists, the radius compare and the mask order plain fp32 values with `<`, so
+// an inner-product score is the NEGATED inner product and "smaller is nearer" holds as it does
+// for L2: one fp32 multiply and one fp32 subtract per element, no contraction, no final negation.
+//
+//  coarse_assign<IP>  list[v] = the first l that minimises dist(x[v], c[l]) (nip for IP), the
+//                 exact direct form (subtract, multiply, add per element -- multiply, subtract
+//                 for IP -- j ascending, no contraction).  A workgroup of 256
 //                 threads owns kTR = 128 rows and streams the centroids past them in tiles of
 //                 kTC = 128, both staged kJT = 32 dimensions at a time into LDS with the
 //                 dimension outermost; thread (ty, tx) keeps an 8 x 8 block of sums (rows
@@ -11,7 +20,7 @@
 //                 The running best is a strict `<` in ascending list order; the 16 threads of
 //                 a row combine by (dist, list).  The result does not depend on the grid: a
 //                 row's sums and their order are the same wherever the row falls.
-//  coarse_probe   one workgroup per query, lane = list (the centroids read from a transposed
+//  coarse_probe<IP>  one workgroup per query, lane = list (the centroids read from a transposed
 //                 copy, so a wave's loads are contiguous), the nprobe smallest by (dist, list)
 //                 through the wave-wide list of pqh_topk_dev.h, and the probe list in the CSR
 //                 form the *_ranges calls take written straight from the offsets.
@@ -26,6 +35,8 @@
 //                 (or float4s) of it a step, kResRows rows in flight; the centroids come from L2.
 //  adc_lut_residual  one workgroup per (query, probed list): the residual query q - c[l] staged
 //                 in LDS once, then adc_lut's sum for every one of the m * K entries.
+//  adc_lut_residual_ip  the same tables for the inner product, another shape: a workgroup per
+//                 (query, slice of the table), the probe's bias folded into part 0.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -56,6 +67,7 @@ constexpr int kStride = kTR + 4;    // floats between two dimensions of a staged
 static_assert(kTR == kTC && kTR == 16 * kR && kTC == 16 * kC, "256 threads as 16 x 16");
 constexpr int kResidualMaxD = PQH_ADC_RESIDUAL_MAX_D;   // the residual query in LDS: 64 KB
 
+template <bool IP>
 __global__ void __launch_bounds__(256, 2)
 coarse_assign(const float* __restrict__ x, long long n, long long ld_x,
               const float* __restrict__ cent, int nlist, int d, int32_t* __restrict__ list,
@@ -110,8 +122,12 @@ coarse_assign(const float* __restrict__ x, long long n, long long ld_x,
                 for (int r = 0; r < kR; ++r)
 #pragma unroll
                     for (int c = 0; c < kC; ++c) {
-                        const float t = xv[r] - cv[c];
-                        acc[r][c] = acc[r][c] + t * t;
+                        if constexpr (IP) {
+                            acc[r][c] = acc[r][c] - xv[r] * cv[c];
+                        } else {
+                            const float t = xv[r] - cv[c];
+                            acc[r][c] = acc[r][c] + t * t;
+                        }
                     }
             }
         }
@@ -155,6 +171,7 @@ coarse_assign(const float* __restrict__ x, long long n, long long ld_x,
 // sixteen waves: 1,024 lists are one step of every wave (the kernel is latency, not
 // throughput: one query keeps one compute unit busy for the length of one list's sum)
 constexpr int kProbeWaves = 16;
+template <bool IP>
 __global__ void __launch_bounds__(64 * kProbeWaves)
 coarse_probe(const float* __restrict__ queries, long long nq, long long ld_q,
              const float* __restrict__ cent_t, int nlist, int d, int nprobe,
@@ -177,8 +194,12 @@ coarse_probe(const float* __restrict__ queries, long long nq, long long ld_q,
         float acc = 0.f;
 #pragma unroll 8
         for (int j = 0; j < d; ++j) {
-            const float t = x[j] - c[(long long)j * nlist];
-            acc = acc + t * t;
+            if constexpr (IP) {
+                acc = acc - x[j] * c[(long long)j * nlist];
+            } else {
+                const float t = x[j] - c[(long long)j * nlist];
+                acc = acc + t * t;
+            }
         }
         list_offer<false>(e, acc, (long long)l, valid, kth);
     }
@@ -347,6 +368,80 @@ adc_lut_residual(const float* __restrict__ queries, long long ld_q, int nprobe,
     }
 }
 
+// The inner-product tables of a residual index, lut[o] as above.  <q, c[l] + r> = <q, c[l]> +
+// <q, r>: the second term is the plain table of the query, the same for every probe, the first
+// one number per probe.  That number is folded into part 0 of the probe's table (bias + entry,
+// one add), so the scan's sum over the parts carries it without a new scan form.
+// Workgroup (q, s): query q, the table entries [s * kLutPer * 256, (s + 1) * kLutPer * 256): it
+// computes their plain values once, keeps them in registers and writes them nprobe times.
+// K <= 256 <= kLutPer * 256, so part 0 lies in the workgroups s == 0 and only they need the
+// biases.  The probes go through LDS 256 at a time (nprobe has no upper bound here): thread t
+// of a round owns probe p0 + t, runs its d-long chain (s == 0, the query staged in LDS) and
+// leaves (bias, valid) for the workgroup, which then writes that round's tables, a wave storing
+// 64 consecutive floats.
+constexpr int kLutPer = 4;
+__global__ void __launch_bounds__(256)
+adc_lut_residual_ip(const float* __restrict__ queries, long long ld_q, int nprobe,
+                    const long long* __restrict__ probes, const float* __restrict__ coarse,
+                    int nlist, const float* __restrict__ cent, int m, int k, int dsub,
+                    float* __restrict__ lut, unsigned long long* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) float qs[];   // the query row, m * dsub floats
+    __shared__ float bias[256];
+    __shared__ unsigned char ok[256];
+    const int tid = threadIdx.x;
+    const long long q = blockIdx.x;
+    const int s = blockIdx.y;
+    const int per = m * k, d = m * dsub;
+    const float* __restrict__ x = queries + q * ld_q;
+    for (int j = tid; j < d; j += 256) qs[j] = x[j];
+    lds_barrier();
+
+    // the thread's entries of the plain table
+    float val[kLutPer];
+#pragma unroll
+    for (int u = 0; u < kLutPer; ++u) {
+        const int e = (s * kLutPer + u) * 256 + tid;
+        float acc = 0.f;
+        if (e < per) {
+            const float* r = qs + (e / k) * dsub;
+            const float* c = cent + (long long)e * dsub;
+            for (int j = 0; j < dsub; ++j) acc = acc - r[j] * c[j];
+        }
+        val[u] = acc;
+    }
+
+#pragma unroll 1
+    for (int p0 = 0; p0 < nprobe; p0 += 256) {
+        const int pn = min(256, nprobe - p0);
+        if (p0) __syncthreads();   // the round before has read bias and ok
+        if (tid < pn) {
+            const long long l = probes[q * nprobe + p0 + tid];
+            const bool good = l >= 0 && l < nlist;
+            float acc = 0.f;
+            if (good && s == 0) {
+                const float* __restrict__ cl = coarse + l * d;
+#pragma unroll 8
+                for (int j = 0; j < d; ++j) acc = acc - qs[j] * cl[j];
+            }
+            if (!good && l != -1 && s == 0) atomicOr(err, 1ull);
+            bias[tid] = acc;
+            ok[tid] = good;
+        }
+        lds_barrier();
+#pragma unroll 1
+        for (int p = 0; p < pn; ++p) {
+            float* __restrict__ dst = lut + (q * nprobe + p0 + p) * per;
+            const bool good = ok[p];
+            const float b = bias[p];
+#pragma unroll
+            for (int u = 0; u < kLutPer; ++u) {
+                const int e = (s * kLutPer + u) * 256 + tid;
+                if (e < per) dst[e] = !good ? INFINITY : e < k ? b + val[u] : val[u];
+            }
+        }
+    }
+}
+
 // bit i of the mask = keep[perm ? perm[i] : i] != 0: one lane per row, the wave's 64 bits by a
 // ballot, its two words stored by lanes 0 and 1 (the bits from n on in the last word are zero).
 // A perm entry outside [0, n) reads nothing, gives a zero bit and sets the error word.
@@ -369,6 +464,75 @@ mask_pack(const unsigned char* __restrict__ keep, const long long* __restrict__ 
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// the entry points that come in an L2 and an inner-product form: one text, the metric picks the
+// instantiation
+int coarse_assign_call(bool ip, pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x,
+                       long long n, long long ld_x, int32_t* d_list, float* d_dist) {
+    if (!ctx) return pqh_no_ctx_status();
+    if (!cq || n < 0 || ld_x < cq->d || (n > 0 && (!d_x || !d_list))) return PQH_ERR_ARG;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (n == 0) return PQH_OK;
+    const long long blocks = (n + kTR - 1) / kTR;
+    if (blocks > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(ip ? coarse_assign<true> : coarse_assign<false>, dim3((unsigned)blocks),
+                       dim3(256), 0, ctx->stream, d_x, n, ld_x, cq->d_cent, cq->nlist, cq->d,
+                       d_list, d_dist);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int coarse_probe_call(bool ip, pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_queries,
+                      long long nq, long long ld_q, int nprobe, const long long* d_offsets,
+                      long long* d_range_ptr, long long* d_ranges, long long* d_probes,
+                      float* d_probe_dist) {
+    if (!ctx) return pqh_no_ctx_status();
+    if (!cq || nq < 0 || ld_q < cq->d || nprobe < 1 || nprobe > PQH_IVF_MAX_NPROBE ||
+        (nq > 0 && (!d_queries || !d_offsets || !d_range_ptr || !d_ranges)))
+        return PQH_ERR_ARG;
+    if (nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (nq == 0) return PQH_OK;
+    hipLaunchKernelGGL(ip ? coarse_probe<true> : coarse_probe<false>, dim3((unsigned)nq),
+                       dim3(64, kProbeWaves), 0, ctx->stream, d_queries, nq, ld_q, cq->d_cent_t,
+                       cq->nlist, cq->d, nprobe, d_offsets, d_range_ptr, d_ranges, d_probes,
+                       d_probe_dist, ctx->d_diag + kDiagIvf);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int adc_tables_residual_call(bool ip, pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse_t* cq,
+                             const float* d_queries, long long nq, long long ld_q,
+                             const long long* d_probes, int nprobe, float* d_lut) {
+    if (!ctx) return pqh_no_ctx_status();
+    int m = 0, k = 0, dsub = 0;
+    const float* d_cent = nullptr;
+    if (pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || !cq || (long long)m * dsub != cq->d || nq < 0 ||
+        nprobe < 1 || ld_q < cq->d || (nq > 0 && (!d_queries || !d_probes || !d_lut)))
+        return PQH_ERR_ARG;
+    if (k > 256 || cq->d > kResidualMaxD || nq * nprobe > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
+    int rc = pqh_use_device(ctx);
+    if (rc) return rc;
+    if (nq == 0) return PQH_OK;
+    if (ip) {
+        const long long slices = ((long long)m * k + kLutPer * 256 - 1) / (kLutPer * 256);
+        if (slices > 65535) return PQH_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(adc_lut_residual_ip, dim3((unsigned)nq, (unsigned)slices), dim3(256),
+                           (size_t)cq->d * 4, ctx->stream, d_queries, ld_q, nprobe, d_probes,
+                           cq->d_cent, cq->nlist, d_cent, m, k, dsub, d_lut,
+                           ctx->d_diag + kDiagIvf);
+    } else {
+        const int vec = dsub % 4 == 0 && !(reinterpret_cast<uintptr_t>(d_cent) & 15u);
+        hipLaunchKernelGGL(adc_lut_residual, dim3((unsigned)(nq * nprobe)), dim3(256),
+                           (size_t)cq->d * 4, ctx->stream, d_queries, ld_q, nprobe, d_probes,
+                           cq->d_cent, cq->nlist, d_cent, m, k, dsub, vec, d_lut,
+                           ctx->d_diag + kDiagIvf);
+    }
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
 }  // namespace
 
 int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_cent) {
@@ -376,12 +540,6 @@ int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_
     *nlist = cq->nlist;
     *d = cq->d;
     *d_cent = cq->d_cent;
-    return PQH_OK;
-}
-
-int pqh_coarse_view_t(const pqh_coarse_t* cq, const float** d_cent_t) {
-    if (!cq) return PQH_ERR_ARG;
-    *d_cent_t = cq->d_cent_t;
     return PQH_OK;
 }
 
@@ -441,17 +599,12 @@ int pqh_coarse_destroy(pqh_coarse_t* cq) {
 
 int pqh_coarse_assign(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
                       long long ld_x, int32_t* d_list, float* d_dist) {
-    if (!ctx) return pqh_no_ctx_status();
-    if (!cq || n < 0 || ld_x < cq->d || (n > 0 && (!d_x || !d_list))) return PQH_ERR_ARG;
-    int rc = pqh_use_device(ctx);
-    if (rc) return rc;
-    if (n == 0) return PQH_OK;
-    const long long blocks = (n + kTR - 1) / kTR;
-    if (blocks > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(coarse_assign, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_x, n,
-                       ld_x, cq->d_cent, cq->nlist, cq->d, d_list, d_dist);
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
+    return coarse_assign_call(false, ctx, cq, d_x, n, ld_x, d_list, d_dist);
+}
+
+int pqh_coarse_assign_ip(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
+                         long long ld_x, int32_t* d_list, float* d_dist) {
+    return coarse_assign_call(true, ctx, cq, d_x, n, ld_x, d_list, d_dist);
 }
 
 int pqh_ivf_layout(pqh_ctx_t* ctx, const int32_t* d_list, long long n, int nlist,
@@ -490,19 +643,16 @@ int pqh_coarse_probe(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_quer
                      long long ld_q, int nprobe, const long long* d_offsets,
                      long long* d_range_ptr, long long* d_ranges, long long* d_probes,
                      float* d_probe_dist) {
-    if (!ctx) return pqh_no_ctx_status();
-    if (!cq || nq < 0 || ld_q < cq->d || nprobe < 1 || nprobe > PQH_IVF_MAX_NPROBE ||
-        (nq > 0 && (!d_queries || !d_offsets || !d_range_ptr || !d_ranges)))
-        return PQH_ERR_ARG;
-    if (nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
-    int rc = pqh_use_device(ctx);
-    if (rc) return rc;
-    if (nq == 0) return PQH_OK;
-    hipLaunchKernelGGL(coarse_probe, dim3((unsigned)nq), dim3(64, kProbeWaves), 0, ctx->stream,
-                       d_queries, nq, ld_q, cq->d_cent_t, cq->nlist, cq->d, nprobe, d_offsets,
-                       d_range_ptr, d_ranges, d_probes, d_probe_dist, ctx->d_diag + kDiagIvf);
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
+    return coarse_probe_call(false, ctx, cq, d_queries, nq, ld_q, nprobe, d_offsets, d_range_ptr,
+                             d_ranges, d_probes, d_probe_dist);
+}
+
+int pqh_coarse_probe_ip(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_queries,
+                        long long nq, long long ld_q, int nprobe, const long long* d_offsets,
+                        long long* d_range_ptr, long long* d_ranges, long long* d_probes,
+                        float* d_probe_dist) {
+    return coarse_probe_call(true, ctx, cq, d_queries, nq, ld_q, nprobe, d_offsets, d_range_ptr,
+                             d_ranges, d_probes, d_probe_dist);
 }
 
 int pqh_ivf_residuals(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
@@ -530,23 +680,15 @@ int pqh_ivf_residuals(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, 
 int pqh_adc_tables_residual(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse_t* cq,
                             const float* d_queries, long long nq, long long ld_q,
                             const long long* d_probes, int nprobe, float* d_lut) {
-    if (!ctx) return pqh_no_ctx_status();
-    int m = 0, k = 0, dsub = 0;
-    const float* d_cent = nullptr;
-    if (pqh_pq_view(pq, &m, &k, &dsub, &d_cent) || !cq || (long long)m * dsub != cq->d || nq < 0 ||
-        nprobe < 1 || ld_q < cq->d || (nq > 0 && (!d_queries || !d_probes || !d_lut)))
-        return PQH_ERR_ARG;
-    if (k > 256 || cq->d > kResidualMaxD || nq * nprobe > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
-    int rc = pqh_use_device(ctx);
-    if (rc) return rc;
-    if (nq == 0) return PQH_OK;
-    const int vec = dsub % 4 == 0 && !(reinterpret_cast<uintptr_t>(d_cent) & 15u);
-    hipLaunchKernelGGL(adc_lut_residual, dim3((unsigned)(nq * nprobe)), dim3(256),
-                       (size_t)cq->d * 4, ctx->stream, d_queries, ld_q, nprobe, d_probes,
-                       cq->d_cent, cq->nlist, d_cent, m, k, dsub, vec, d_lut,
-                       ctx->d_diag + kDiagIvf);
-    PQH_LAUNCH_CHECK(ctx);
-    return PQH_OK;
+    return adc_tables_residual_call(false, ctx, pq, cq, d_queries, nq, ld_q, d_probes, nprobe,
+                                    d_lut);
+}
+
+int pqh_adc_tables_residual_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq, const pqh_coarse_t* cq,
+                               const float* d_queries, long long nq, long long ld_q,
+                               const long long* d_probes, int nprobe, float* d_lut) {
+    return adc_tables_residual_call(true, ctx, pq, cq, d_queries, nq, ld_q, d_probes, nprobe,
+                                    d_lut);
 }
 
 int pqh_mask_pack(pqh_ctx_t* ctx, const unsigned char* d_keep, const long long* d_perm, long long n,

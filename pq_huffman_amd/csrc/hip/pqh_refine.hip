@@ -7,7 +7,7 @@
 // The inner-product form (pqh_refine_*_ip, the IP instantiations) scores the same candidates by
 //   nip(q, r) = acc,  acc = +0;  acc = acc - q[j] * (c1[a][j] + c2[b][j])
 // (residual index: c[list(r)][j] + (c1[a][j] + c2[b][j])), the negated inner product of
-// pqh_metric.hip, one chain over d; decode, select and errors are shared with the L2 form.
+// pqh_ivf.hip's header, one chain over d; decode, select and errors are shared with the L2 form.
 //
 //  refine_rows   one workgroup of two waves per query, one candidate per lane.
 //                Decode: wave 0 reaches the lane's row of the level-1 stream and wave 1 the same

@@ -1,8 +1,10 @@
 // pqh_search.hip -- asymmetric distance (ADC) search of a compressed stream: the decoder of
 // pqh_decode.hip with a scoring phase where its store was.
 //
-//  adc_lut     lut[q][i][c] = ||q_i - cent[i][c]||^2, one thread per entry (the oracle
-//              arithmetic of pqh_pq_assign: fp32, j order, no contraction).
+//  adc_lut<IP> lut[q][i][c] = ||q_i - cent[i][c]||^2, one thread per entry (the oracle
+//              arithmetic of pqh_pq_assign: fp32, j order, no contraction).  IP = 1
+//              (pqh_adc_tables_ip): the negated inner product nip(q_i, cent[i][c]) of
+//              pqh_ivf.hip's header in the entry's place; the scan is the same for both.
 //  adc_scan    one lane per chunk, 64 chunks per wave and step: the chunks' stream window and
 //              their decoded rows staged in the wave's LDS (stage_step; the walks are
 //              pqh_decode_dev.h's), then every row scored against a batch of QB query tables
@@ -50,6 +52,7 @@
 
 namespace {
 
+template <bool IP>
 __global__ void __launch_bounds__(256)
 adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
         const float* __restrict__ cent, int m, int k, int dsub, float* __restrict__ lut) {
@@ -62,8 +65,12 @@ adc_lut(const float* __restrict__ queries, long long nq, long long ld_q,
     const float* c = cent + (long long)e * dsub;
     float acc = 0.f;
     for (int j = 0; j < dsub; ++j) {
-        const float t = x[j] - c[j];
-        acc = acc + t * t;
+        if constexpr (IP) {
+            acc = acc - x[j] * c[j];
+        } else {
+            const float t = x[j] - c[j];
+            acc = acc + t * t;
+        }
     }
     lut[idx] = acc;
 }
@@ -834,12 +841,8 @@ int search_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k,
                        pr != nullptr, pr && pr->tables, ls);
 }
 
-}  // namespace
-
-extern "C" {
-
-int pqh_adc_tables(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
-                   long long ld_q, float* d_lut) {
+int adc_tables_call(bool ip, pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries,
+                    long long nq, long long ld_q, float* d_lut) {
     if (!ctx) return pqh_no_ctx_status();
     int m = 0, k = 0, dsub = 0;
     const float* d_cent = nullptr;
@@ -852,10 +855,24 @@ int pqh_adc_tables(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, l
     if (nq == 0) return PQH_OK;
     const long long blocks = (nq * m * k + 255) / 256;
     if (blocks > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(adc_lut, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_queries, nq,
-                       ld_q, d_cent, m, k, dsub, d_lut);
+    hipLaunchKernelGGL(ip ? adc_lut<true> : adc_lut<false>, dim3((unsigned)blocks), dim3(256), 0,
+                       ctx->stream, d_queries, nq, ld_q, d_cent, m, k, dsub, d_lut);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pqh_adc_tables(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
+                   long long ld_q, float* d_lut) {
+    return adc_tables_call(false, ctx, pq, d_queries, nq, ld_q, d_lut);
+}
+
+int pqh_adc_tables_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries, long long nq,
+                      long long ld_q, float* d_lut) {
+    return adc_tables_call(true, ctx, pq, d_queries, nq, ld_q, d_lut);
 }
 
 int pqh_search_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,

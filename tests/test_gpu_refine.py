@@ -268,6 +268,64 @@ def test_a_row_outside_the_stream_is_dropped_and_reported(gpu, small):
         codec.decode_status(ctx)                                                 # read once, then clean
 
 
+@pytest.mark.parametrize("extra", [0, 100])
+def test_a_row_past_the_last_list_is_dropped_and_reported(gpu, extra):
+    """a residual re-rank whose offsets do not cover the stream: the offsets of rr.residual_world(15)
+    from the end of the last non-empty list on (offsets[nlist] and the empty lists before it, so
+    that they still ascend) lowered by three rows.  That list keeps a row and every row below the
+    new end keeps its list; a candidate at or above it is inside [0, n) and is decoded, finds no
+    list, is dropped and sets PQH_ERR_ARG, in a query's first and last slot too.  Expected: the
+    mirrors with those candidates as rows outside the stream.  extra = 0: about 30 candidates,
+    refine_rows; extra = 100: about 130, refine_rows_wide on a context whose limit is raised."""
+    import metric_ref as mref
+    torch, codec, ctx = gpu
+    w = rr.residual_world(15)
+    rr.check_residual_world(w)
+    off, nlist = w["offsets"], len(w["offsets"]) - 1
+    cut = rr.N - 3
+    low = np.minimum(off, cut)
+    last = int(np.flatnonzero(np.diff(off) > 0)[-1])      # the last non-empty list
+    assert low[nlist] == cut < off[nlist] and (np.diff(low) >= 0).all()
+    assert low[last] == off[last] < cut and np.array_equal(low[:last + 1], off[:last + 1])
+    below = np.arange(cut)
+    assert np.array_equal(rr.lists_of(low, below), rr.lists_of(off, below))
+    assert (rr.lists_of(low, np.arange(cut, rr.N)) >= nlist).all()
+
+    rng = np.random.default_rng(77 + extra)
+    rows = np.concatenate([w["rows"], rng.integers(0, rr.N, size=(5, extra))], axis=1)
+    ncand = rows.shape[1]
+    assert (ncand <= 64) if extra == 0 else (64 < ncand <= 256)
+    rows[0, 0], rows[2, -1], rows[4, 0], rows[4, -1] = cut, rr.N - 1, cut + 1, cut
+    assert (rows[1] >= cut).any() and (rows[3] >= cut).any()     # (rr.N - 1 is in every query)
+    outside = np.where(rows >= cut, rr.N, rows)
+    streams, plain = _levels(gpu, w)
+    cq = codec.Coarse(ctx, w["coarse"])
+    qd, rd = torch.from_numpy(w["q"]).cuda(), torch.from_numpy(rows).cuda()
+    od = torch.from_numpy(low).cuda()
+    limit = ctx.search_max_k
+    if ncand > limit:
+        ctx.set_search_max_k(256)
+    try:
+        codec.decode_status(ctx)
+        case = 0
+        for fn, mirror in ((codec.refine, rr.refine), (codec.refine_ip, mref.refine)):
+            for k in (10, ncand):
+                want = mirror(w["q"], outside, k, w["cent1"], w["codes1"], w["cent2"], w["codes2"],
+                              w["coarse"], off)
+                if k == ncand:                            # the dropped ones are the padding
+                    assert ((want[1] == -1).sum(axis=1) == (rows >= cut).sum(axis=1)).all()
+                for levels in (streams, plain):
+                    got = fn(ctx, *levels, qd, rd, k, coarse=cq, offsets=od,
+                             out=_out(torch, 5, k, POISON[case % 3]))
+                    case += 1
+                    _check(got, want, (fn.__name__, extra, k))
+                    assert _status(lambda: codec.decode_status(ctx)) == -1       # PQH_ERR_ARG
+                    codec.decode_status(ctx)                                     # read once, then clean
+    finally:
+        ctx.set_search_max_k(limit)
+    cq.close()
+
+
 def test_a_corrupt_level_two_chunk_drops_its_candidates_only(gpu, small):
     """a level-2 chunk offset past the stream's end: the candidate in that chunk is dropped and
     PQH_ERR_CORRUPT reported (before a bad row's PQH_ERR_ARG); the other queries' results are the
