@@ -771,15 +771,188 @@ struct GrpHeap {
     }
 };
 
+// ---- the leaf heap by level passes (PQH_TREE_LEAFSCAN; 0 = one push per symbol) ----------
+// A push (huffman_encode.c:33-46) read from the root down: the entry walks the path to its
+// slot t, takes the first node strictly heavier than it, and from there every displaced
+// occupant takes the next node of the path; the last one lands in slot t.  So a node only
+// filters the entries that arrive at it, in push order, and the nodes of a level do not
+// interact: the heap after all pushes is one pass per level instead of one dependent LDS
+// round trip per symbol.  At node v (depth l) the arrivals are the t whose depth-l ancestor
+// is v, in increasing t (rank q = 1, 2, ...: t = ((v - 1) << floor(log2 q)) + q).  The
+// first fills the node.  A later one that is below everything before it in the order
+//     (weight, displaced ? 255 - t : 256 + t)
+// becomes the occupant and sends the previous occupant on towards t, displaced; any other
+// goes on itself.  (An entry still looking for its node takes it only from a strictly
+// heavier one; a displaced occupant, never heavier than what lies below it, takes it from
+// any equal weight, a later one from an earlier one.)  The occupant after the last arrival
+// is heap[v]; what was sent on are the arrivals of level l + 1.
+// Of the tie word only the displaced bit is kept: the rest says which of two arrivals came
+// first, and every compare here knows that from where it stands -- inside a lane's run from
+// the order of the ranks, between runs from the order of the lanes.  So a word is the heap
+// key weight << 10 | symbol with bit 9 set while the entry still looks for its node, a slot
+// is one u32, and "y, the later one, takes the node from x" is leaf_takes(y, x & ~511).
+// Arrival t lives in word t of `w` (the kid region, free until the first merge; word 0 is
+// nobody's) and is overwritten by what it sends on.  Words past the last leaf are all ones:
+// such an arrival takes no node and sends itself on, so no pass asks how many leaves there
+// are.  The passes cover slots 1-255 -- the ranks of a node then are 2^k - 1, whole aligned
+// vectors: ranks 1, 2-3, 4-7, 8-15 of node v lie at v, 2v, 4v, 8v, ranks 16s .. 16s + 15 in
+// 16 consecutive words -- and symbol 256 of a full alphabet is pushed after them.
+// tests/leafscan_ref.py has the order, this schedule and the push loop side by side.
+#ifndef PQH_TREE_LEAFSCAN
+#define PQH_TREE_LEAFSCAN 1
+#endif
+// arrival y against the occupant's compare form xm (its word & ~511; all ones: no occupant)
+__device__ __forceinline__ bool leaf_takes(uint32_t y, uint32_t xm) {
+    return y - (~y & 512u) < xm;
+}
+// N arrivals of one node in rank order; kSend: each is replaced by what it sends on
+template <int N, bool kSend>
+__device__ __forceinline__ void leaf_filter(uint32_t* x, uint32_t& occ, uint32_t& occm) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const bool take = leaf_takes(x[u], occm);
+        const uint32_t out = take ? occ & ~512u : x[u];
+        occ = take ? x[u] : occ;
+        occm = take ? x[u] & ~511u : occm;
+        if (kSend) x[u] = out;
+    }
+}
+__device__ __forceinline__ void leaf_get(uint32_t* x, const uint32_t* p, int n) {   // n = 1, 2, 4
+    if (n == 1) x[0] = p[0];
+    if (n == 2) {
+        const uint2 q = *reinterpret_cast<const uint2*>(p);
+        x[0] = q.x, x[1] = q.y;
+    }
+    if (n == 4) {
+        const uint4 q = *reinterpret_cast<const uint4*>(p);
+        x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+    }
+}
+__device__ __forceinline__ void leaf_put(const uint32_t* x, uint32_t* p, int n) {
+    if (n == 1) p[0] = x[0];
+    if (n == 2) *reinterpret_cast<uint2*>(p) = make_uint2(x[0], x[1]);
+    if (n == 4) *reinterpret_cast<uint4*>(p) = make_uint4(x[0], x[1], x[2], x[3]);
+}
+// Levels 4-7: a lane owns 1, 2, 4, 8 whole nodes (v = 2^L + gl, + 16, ...) with 15, 7, 3, 1
+// arrivals each.  kBatch nodes at a time, their reads first (level 4: ranks 1-7, then 8-15):
+// as many words in flight as the 32 registers allow.
+template <int L>
+__device__ __forceinline__ void leaf_own(uint32_t* h, uint32_t* w, int n, int gl) {
+    constexpr int kNodes = 1 << (L - 4), kLo = L == 7 ? 1 : L == 6 ? 3 : 7;
+    constexpr int kBatch = L == 7 ? 4 : L == 6 ? 2 : 1;
+#pragma unroll
+    for (int i0 = 0; i0 < kNodes; i0 += kBatch) {
+        uint32_t x[kBatch][kLo];
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) {
+            const int v = (1 << L) + gl + 16 * (i0 + i);
+            leaf_get(x[i], w + v, 1);
+            if (L < 7) leaf_get(x[i] + 1, w + 2 * v, 2);
+            if (L < 6) leaf_get(x[i] + 3, w + 4 * v, 4);
+        }
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) {
+            const int v = (1 << L) + gl + 16 * (i0 + i);
+            uint32_t occ = GrpHeap::kMax, occm = GrpHeap::kMax;
+            leaf_filter<kLo, true>(x[i], occ, occm);   // (rank 1 fills the node: not written)
+            if (L < 7) leaf_put(x[i] + 1, w + 2 * v, 2);
+            if (L < 6) leaf_put(x[i] + 3, w + 4 * v, 4);
+            if (L == 4) {
+                uint32_t z[8];
+                leaf_get(z, w + 8 * v, 4);
+                leaf_get(z + 4, w + 8 * v + 4, 4);
+                leaf_filter<8, true>(z, occ, occm);
+                leaf_put(z, w + 8 * v, 4);
+                leaf_put(z + 4, w + 8 * v + 4, 4);
+            }
+            if (v <= n) h[v] = occ & ~512u;
+        }
+        asm volatile("" ::: "memory");   // (the next batch's reads not drawn up into this one)
+    }
+    wave_sync_lds();
+}
+// h[1 .. n] = the heap after pushing the words w[1 .. n] in that order (n <= 255)
+__device__ __forceinline__ void grp_leaves(uint32_t* h, uint32_t* w, int n, int gl) {
+    constexpr uint32_t kMax = GrpHeap::kMax;
+    // levels 0-3 (1, 2, 4, 8 nodes): 16 >> l lanes per node, 16 consecutive ranks per lane.
+    // A lane's words are b + j * mul, j = 0 .. 15: the node's first lane has ranks 1-15
+    // (and word 0 for rank 0), the others 16 consecutive words.
+    for (int l = 0; l < 4 && (1 << l) <= n; ++l) {
+        const int sl = gl & (15 >> l);
+        const int v = (1 << l) + (gl >> (4 - l));
+        const int b = sl ? ((v - 1) << (35 - __clz(sl))) + 16 * sl : 0;
+        const int mul = sl ? 1 : v;
+        uint32_t* const p = w + b;
+        uint32_t x[8];
+        // the run's occupant, had the node been empty
+        uint32_t m = kMax, mm = kMax;
+        leaf_get(x, p, 1);
+        leaf_get(x + 1, p + mul, 1);
+        leaf_get(x + 2, p + 2 * mul, 2);
+        leaf_get(x + 4, p + 4 * mul, 4);
+        leaf_filter<8, false>(x, m, mm);
+        asm volatile("" ::: "memory");   // (eight words in flight, not sixteen: the registers)
+        leaf_get(x, p + 8 * mul, 4);
+        leaf_get(x + 4, p + 8 * mul + 4, 4);
+        leaf_filter<8, false>(x, m, mm);
+        // ... the occupant after the runs up to this lane's: a scan inside the node's lanes
+        // (row_shr 1, 2, 4, 8; y = the earlier lanes' occupant, which m may take over)
+        uint32_t y;
+#define PQH_LEAF_SCAN_STEP(CTRL, D)                                                       \
+        y = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)m, CTRL, 0xF, 0xF, false);     \
+        m = sl >= D && !leaf_takes(m, y & ~511u) ? y : m;
+        PQH_LEAF_SCAN_STEP(0x111, 1)
+        PQH_LEAF_SCAN_STEP(0x112, 2)
+        PQH_LEAF_SCAN_STEP(0x114, 4)
+        PQH_LEAF_SCAN_STEP(0x118, 8)
+#undef PQH_LEAF_SCAN_STEP
+        // the node's last lane holds the occupant after every arrival
+        if (sl == (15 >> l) && v <= n) h[v] = m & ~512u;
+        // ... and after the runs before it: what this lane's first arrival meets
+        y = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)m, 0x111, 0xF, 0xF, false);
+        uint32_t occ = sl ? y : kMax;
+        uint32_t occm = sl ? y & ~511u : kMax;
+        // (four words at a time: with eight, the filter's outputs take the build past the
+        // registers the assignment grid leaves)
+        leaf_get(x, p, 1);
+        leaf_get(x + 1, p + mul, 1);
+        leaf_get(x + 2, p + 2 * mul, 2);
+        leaf_filter<4, true>(x, occ, occm);
+        leaf_put(x, p, 1);   // (the first lane: all ones into word 0)
+        leaf_put(x + 1, p + mul, 1);
+        leaf_put(x + 2, p + 2 * mul, 2);
+#pragma unroll
+        for (int j = 4; j < 16; j += 4) {
+            uint32_t* const pj = j < 8 ? p + 4 * mul : p + 8 * mul + (j - 8);
+            leaf_get(x, pj, 4);
+            leaf_filter<4, true>(x, occ, occm);
+            leaf_put(x, pj, 4);
+        }
+        wave_sync_lds();
+    }
+    if (n >= 16) leaf_own<4>(h, w, n, gl);
+    if (n >= 32) leaf_own<5>(h, w, n, gl);
+    if (n >= 64) leaf_own<6>(h, w, n, gl);
+    if (n >= 128) leaf_own<7>(h, w, n, gl);
+}
+
 // leaves (pushed in symbol order), merges; returns the internal-node count
 __device__ __forceinline__ int grp_merge(GrpHeap& hp, const unsigned long long* lkey, int nz,
                                          uint32_t* kid, bool stamp) {
     constexpr uint32_t kLow = GrpHeap::kLow;
+#if PQH_TREE_LEAFSCAN
+    hp.n = min(nz, 255);   // (grp_leaves has run)
+    if (nz == 256) {
+        const uint32_t a = hp.anc();
+        hp.push((uint32_t)lkey[255], a);
+    }
+#else
     for (int j = 0; j < nz; ++j) {
         const uint32_t a = hp.anc();
         const uint32_t e = (uint32_t)lkey[j];   // (read in the same round trip as the ancestors)
         hp.push(e, a);
     }
+#endif
     if (stamp) g_tree_stamps[2] = __builtin_amdgcn_s_memtime();
     int next = 0;
     if (hp.n == 1) {   // lone symbol: code "0" (huffman_encode.c:168-177)
@@ -909,7 +1082,9 @@ huff_trees_grp(const uint32_t* __restrict__ counts, int k, long long trees,
     unsigned long long* lkey = reinterpret_cast<unsigned long long*>(base + kGrpHeapBytes + kGrpKidBytes);
     {   // sentinels: every heap slot all ones (u32 and u64 views alike)
         uint4* z = reinterpret_cast<uint4*>(base);
-        for (int q = gl; q < kGrpHeapBytes / 16; q += 16) z[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        // (and, behind the heap, every word of the level passes)
+        constexpr int kOnes = kGrpHeapBytes + (PQH_TREE_LEAFSCAN ? kGrpKidBytes : 0);
+        for (int q = gl; q < kOnes / 16; q += 16) z[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
     }
     if (grp >= trees) return;   // no workgroup barriers below
     // latency-bound: issue ahead of the (older, VALU-bound) assignment waves on the SIMD
@@ -924,7 +1099,13 @@ huff_trees_grp(const uint32_t* __restrict__ counts, int k, long long trees,
         const int s = s0 + gl;
         const uint32_t c = s < k ? cnt[s] : 0u;
         const uint32_t mb = grp_bits(c != 0u, gsh);
-        if (c) lkey[nz + __popc(mb & ((1u << gl) - 1u))] = ((unsigned long long)c << 10) | (unsigned)s;
+        if (c) {
+            const int j = nz + __popc(mb & ((1u << gl) - 1u));
+            lkey[j] = ((unsigned long long)c << 10) | (unsigned)s;
+#if PQH_TREE_LEAFSCAN   // the level passes' word (grp_leaves; a tree too heavy for it is not scanned)
+            if (j < 255) kid[j + 1] = (c << 10) | 512u | (unsigned)s;
+#endif
+        }
         nz += __popc(mb);
         total += c;
     }
@@ -936,19 +1117,28 @@ huff_trees_grp(const uint32_t* __restrict__ counts, int k, long long trees,
     unsigned long long* code = reinterpret_cast<unsigned long long*>(base);   // (after the merges)
     int nint = 0;
     if (nz > 0 && !heavy) {
-        // lane constants of the stretch: node gl's depth, its ancestors and the directions
+#if PQH_TREE_LEAFSCAN
+        // the heap of the leaves, before the merges' lane constants exist (the lane index
+        // made opaque after it, so they are not computed early and held through the passes)
+        grp_leaves(reinterpret_cast<uint32_t*>(base), kid, min(nz, 255), gl);
+        int gm = gl;
+        asm volatile("" : "+v"(gm));
+#else
+        const int gm = gl;
+#endif
+        // lane constants of the stretch: node gm's depth, its ancestors and the directions
         // towards it; lane 0 stands for no node (its node lies past the heap and its
         // direction bit, 0, never matches E)
-        const int dq = gl ? 31 - __clz(gl) : 8;
-        const int off = gl ? gl - (1 << dq) : 0;
-        uint32_t A = gl ? 0u : 1u, E = gl ? 0u : 1u;
-        for (int j = 1; j <= (gl ? dq : 0); ++j) {
-            A |= 1u << (gl >> j);
-            E |= (uint32_t)((gl >> (j - 1)) & 1) << (gl >> j);
+        const int dq = gm ? 31 - __clz(gm) : 8;
+        const int off = gm ? gm - (1 << dq) : 0;
+        uint32_t A = gm ? 0u : 1u, E = gm ? 0u : 1u;
+        for (int j = 1; j <= (gm ? dq : 0); ++j) {
+            A |= 1u << (gm >> j);
+            E |= (uint32_t)((gm >> (j - 1)) & 1) << (gm >> j);
         }
         uint32_t* h = reinterpret_cast<uint32_t*>(base);
-        if (gl == 0) h[0] = 0u;   // position 0: the missing ancestor
-        GrpHeap hp{h, 0, gl, gsh, dq, off, A, E};
+        if (gm == 0) h[0] = 0u;   // position 0: the missing ancestor
+        GrpHeap hp{h, 0, gm, gsh, dq, off, A, E};
         nint = grp_merge(hp, lkey, nz, kid, stamp);
     } else if (nz > 0) {
         if (gl == 0) nint = grp_merge_heavy(reinterpret_cast<unsigned long long*>(base), lkey, nz, kid);
