@@ -1147,8 +1147,14 @@ pq_assign_mfma(const float* __restrict__ x, long long n, long long ldx, int m_to
             const bool valid = rowl < n;   // rows past n hold row n - 1 (clamped loads)
             const bool own_lane = pair || h == 0;
             const float Xl = Xg[g];
-            const bool finite = isfinite(Xl);
             const float tau = screen_tau(Xl, pair && h ? any_lo[bb] : any_lo[ba], tq);
+            // "finite": X is, and no screening score of the vector can have overflowed.  Every
+            // partial sum of a score is at most Cmax + 2 P <= (sqrt(X) + sqrt(Cmax))^2 in
+            // magnitude, and tau >= 2.2 * 2^-17 times that, so tau < 2^110 keeps them below
+            // 2^127.  Above it (finite x and c of magnitude ~2^62: a score of -inf makes the
+            // queued threshold K1 + tau a NaN that admits no candidate) the vector is re-ranked
+            // inline like a non-finite one.  (false for X = inf or NaN: tau is then inf or NaN)
+            const bool finite = tau < 0x1p110f;
             // a key differs from its score by less than 2^PB ulp (2^(PB-23) relative):
             // 2^(PB-21) of the larger magnitude covers both keys of the gap (and the rounding
             // of K2 - K1)
