@@ -812,6 +812,25 @@ int pqh_adc_tables_ip(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_queries
  * go to the smaller l); d_dist (optional) that value -- see pqh_coarse_assign. */
 int pqh_coarse_assign_ip(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
                          long long ld_x, int32_t* d_list, float* d_dist);
+/* What pqh_coarse_assign / pqh_coarse_assign_ip compute, d_list and d_dist bit for bit, by a
+ * bf16-split matrix-instruction screen and an exact finish: every list within a proven error
+ * bound of the screen's best is evaluated by the definition's chain, and the smallest by
+ * (dist, list) wins.  Arguments, argument errors, n == 0, asynchrony and the rule that the floats
+ * between rows are never read are pqh_coarse_assign's.  The first screened call of a quantizer
+ * builds its prepared centroids on the context's stream (8 bytes per list and 4 per list and
+ * dimension, d padded to 16 and nlist to 32), which pqh_coarse_destroy frees.  d above 1024: the
+ * call launches the direct kernel itself.  No workspace. */
+int pqh_coarse_assign_screen(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x, long long n,
+                             long long ld_x, int32_t* d_list, float* d_dist /* may be NULL */);
+int pqh_coarse_assign_screen_ip(pqh_ctx_t* ctx, const pqh_coarse_t* cq, const float* d_x,
+                                long long n, long long ld_x, int32_t* d_list,
+                                float* d_dist /* may be NULL */);
+/* Synchronises: of the last *_screen call on this context that had rows, the rows whose
+ * candidates were evaluated exactly (more than one candidate), and the rows that took the
+ * all-lists path (candidate overflow, a non-finite value, a bound too large to trust a score).
+ * Both 0 after a call that handed over to the direct kernel. */
+int pqh_coarse_last_screen_counts(pqh_ctx_t* ctx, unsigned long long* reranked,
+                                  unsigned long long* fallback);
 /* The nprobe lists by (nip(q, c[l]), l) ascending; the four outputs and the padding of
  * pqh_coarse_probe, d_probe_dist holding the nip values (bit-equal to pqh_coarse_assign_ip's
  * d_dist for nprobe == 1). */

@@ -220,6 +220,10 @@ SIGNATURES = [
     ("pqh_adc_tables_ip", I, [P, P, P, LL, LL, P]),
     ("pqh_coarse_assign_ip", I, [P, P, P, LL, LL, P, P]),
     ("pqh_coarse_probe_ip", I, [P, P, P, LL, LL, I, P, P, P, P, P]),
+    # the screened coarse assignment: the arguments of pqh_coarse_assign, and its counts
+    ("pqh_coarse_assign_screen", I, [P, P, P, LL, LL, P, P]),
+    ("pqh_coarse_assign_screen_ip", I, [P, P, P, LL, LL, P, P]),
+    ("pqh_coarse_last_screen_counts", I, [P, P, P]),
     ("pqh_adc_tables_residual_ip", I, [P, P, P, P, LL, LL, P, I, P]),
     ("pqh_refine_stream_ip", I,
      [P, P, P, P, ULL, I, I, P, P, P, P, P, ULL, I, I, P, P, LL, P, P, P, LL, LL, P, I, I, P, P,

@@ -1132,19 +1132,32 @@ class Coarse:
         # a device copy for torch (the fetch of a residual index adds a row's centroid back)
         self.centroids = _torch().tensor(c, device=f"cuda:{ctx.device}")
 
-    def assign(self, x, out=None, dist=None, metric: str = "l2"):
+    def assign(self, x, out=None, dist=None, metric: str = "l2", method: str = "direct"):
         """list ids int32 (n,) of the rows of x (device float32 (n, >= d)), the nearest
         centroid each (pqh_coarse_assign); dist: an optional float32 (n,) tensor that takes the
         winning distances.  metric="ip": the centroid of the largest inner product, dist its
-        negation (pqh_coarse_assign_ip).  Async."""
+        negation (pqh_coarse_assign_ip).  method="screen": the same bits through the
+        matrix-instruction screen (pqh_coarse_assign_screen; screen_counts() tells how the rows
+        went); any other method but "direct" is a ValueError.  Async."""
         torch = _torch()
-        name = "pqh_coarse_assign" + _metric_suffix(metric, "Coarse.assign")
+        if method not in ("direct", "screen"):
+            raise ValueError(f"Coarse.assign: method {method!r} (\"direct\" or \"screen\")")
+        name = ("pqh_coarse_assign" + ("_screen" if method == "screen" else "") +
+                _metric_suffix(metric, "Coarse.assign"))
         n = x.shape[0]
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=x.device)
         check(getattr(lib(), name)(self.ctx.ptr, self.ptr, _ptr(x), n, x.stride(0), _ptr(out),
                                    _ptr(dist)), name)
         return out
+
+    def screen_counts(self):
+        """(reranked, fallback) of the context's last assign(method="screen") that had rows: the
+        rows with more than one candidate, and the rows that took the all-lists path.  Waits."""
+        a, b = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(lib().pqh_coarse_last_screen_counts(self.ctx.ptr, ctypes.byref(a), ctypes.byref(b)),
+              "pqh_coarse_last_screen_counts")
+        return a.value, b.value
 
     def layout(self, list_ids):
         """(perm, offsets) as ivf_layout gives them, by pqh_ivf_layout: list_ids device int32
@@ -1610,6 +1623,7 @@ class IVF:
         self.n_ids = perm.numel()   # ids ever given out: inv's length; perm's until a compact()
         self.residual = residual
         self.metric = metric        # "l2" or "ip": how rows go to lists and how a search scores
+        self.assign_method = "direct"   # build(assign=...): Coarse.assign's method, add() keeps it
         self.refine_pq = self.refine_tables = self.refine_enc = None   # build(refine_pq=...)
         self.rotation = None     # build(rotation=...): the index lives in the rotated space
         self.live = None         # remove(): device bool per stream row, allocated on first use
@@ -1619,7 +1633,8 @@ class IVF:
     def build(cls, ctx: Context, pq: PQ, coarse: Coarse, x, chunk_vectors: int = 64,
               context: bool = True, residual: bool = False, refine_pq: PQ = None,
               refine_chunk_vectors: int = None, compress_ids: bool = False,
-              metric: str = "l2", rotation: "Rotation" = None) -> "IVF":
+              metric: str = "l2", rotation: "Rotation" = None,
+              assign: str = "direct") -> "IVF":
         """x: device float32 (n, d), d = coarse.d = pq.m * pq.dsub.  The stages: rows to
         lists, layout, gather x[perm] (residual: coarse.residuals(x, lists, perm) in its
         place), pq.assign, histogram, Tables.build, encode.  refine_pq: what pq leaves over
@@ -1630,9 +1645,12 @@ class IVF:
         once at the top, into one extra n x d buffer that lives until build() returns, and
         coarse, pq and refine_pq must hold centroids of rotated rows; PqhError if rotation.d is
         not d or rotation.defect() > 1e-3 (rounding an orthonormal matrix to float32 leaves
-        about d * 2^-24 <= 6e-5)."""
+        about d * 2^-24 <= 6e-5).  assign: Coarse.assign's method, "direct" or "screen" -- the
+        same index either way; it is kept on the index and add() sends its rows the same way."""
         torch = _torch()
         _metric_suffix(metric, "IVF.build")
+        if assign not in ("direct", "screen"):
+            raise ValueError(f"IVF.build: assign {assign!r} (\"direct\" or \"screen\")")
         if rotation is not None:
             if rotation.d != x.shape[1]:
                 raise PqhError(-1, "IVF.build: the rotation and x disagree in d")
@@ -1649,7 +1667,7 @@ class IVF:
                 raise PqhError(-1, "IVF.build: refine_pq and the PQ disagree in d")
         if rotation is not None:
             x = rotation.apply(x)
-        lists = coarse.assign(x, metric=metric)
+        lists = coarse.assign(x, metric=metric, method=assign)
         perm, offsets = coarse.layout(lists)
         rows = coarse.residuals(x, lists, perm) if residual else x[perm]
         codes = pq.assign(rows, ctx=ctx)
@@ -1669,6 +1687,7 @@ class IVF:
         inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=perm.device)
         ivf = cls(ctx, pq, coarse, tables, enc, perm, inv, offsets, residual, metric)
         ivf.rotation = rotation
+        ivf.assign_method = assign
         if refined is not None:
             ivf.refine_pq, (ivf.refine_tables, ivf.refine_enc) = refine_pq, refined
         if compress_ids:
@@ -1736,7 +1755,7 @@ class IVF:
         new rows, the codes in the batch's own list order: the stages of build()"""
         if self.rotation is not None:
             x = self.rotation.apply(x)
-        lists = self.coarse.assign(x, metric=self.metric)
+        lists = self.coarse.assign(x, metric=self.metric, method=self.assign_method)
         perm, offsets = self.coarse.layout(lists)
         rows = self.coarse.residuals(x, lists, perm) if self.residual else x[perm]
         codes = self.pq.assign(rows, ctx=self.ctx)

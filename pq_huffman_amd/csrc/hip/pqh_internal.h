@@ -91,6 +91,16 @@ int pqh_pq_error_accum(pqh_ctx* ctx, const pqh_pq_t* pq, const float* d_x, long 
 // a prepared codebook's shape and its device centroids [m][k][dsub] (pqh_assign.hip), for the
 // fused reconstruction of pqh_fetch_vectors; PQH_ERR_ARG for a null codebook
 int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_cent);
+// the coarse quantizer (pqh_ivf.hip)
+struct pqh_coarse {
+    pqh_ctx* ctx = nullptr;
+    int nlist = 0, d = 0;
+    float* d_cent = nullptr;     // [nlist][d]
+    float* d_cent_t = nullptr;   // [d][nlist]
+    // the prepared centroids of the screened assignment (pqh_coarse_screen.hip): built by the
+    // first pqh_coarse_assign_screen call, null for a quantizer that never takes one
+    void* d_screen = nullptr;
+};
 // a coarse quantizer's shape and its device centroids [nlist][d] (pqh_ivf.hip), for the re-rank
 // of a residual index (pqh_refine.hip); PQH_ERR_ARG for a null quantizer
 int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_cent);

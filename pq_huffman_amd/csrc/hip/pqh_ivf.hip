@@ -49,13 +49,6 @@
 #include "pqh_internal.h"
 #include "pqh_topk_dev.h"
 
-struct pqh_coarse {
-    pqh_ctx* ctx = nullptr;
-    int nlist = 0, d = 0;
-    float* d_cent = nullptr;     // [nlist][d]
-    float* d_cent_t = nullptr;   // [d][nlist]
-};
-
 namespace {
 
 constexpr int kTR = 128;            // rows of a workgroup
@@ -593,6 +586,7 @@ int pqh_coarse_destroy(pqh_coarse_t* cq) {
     }
     if (cq->d_cent) (void)hipFree(cq->d_cent);
     if (cq->d_cent_t) (void)hipFree(cq->d_cent_t);
+    if (cq->d_screen) (void)hipFree(cq->d_screen);
     delete cq;
     return PQH_OK;
 }

@@ -7,7 +7,10 @@ produce the same bits.
 
   assign   --rows x 128 at nlist in {1024, 4096}: ms, and the ratio of the 3 * n * nlist * d
            lane-operations of the direct form to the time (lane-operations per second, and as
-           a share of 256 CUs x 128 lanes at --ghz; the clock the run held is NOT measured)
+           a share of 256 CUs x 128 lanes at --ghz; the clock the run held is NOT measured);
+           beside it method="screen" on the same rows -- the two alternate, --pairs times, the
+           prepared centroids built before (that one-time cost is its own figure), both outputs
+           compared on every row -- on the bench's rows and on a Gaussian set
   layout   --rows and --layout-rows list ids at nlist 1024
   probe    nq in {1, 8, 64, 512}, nprobe 16, nlist 1024, and its share of the search_ranges
            call it feeds on the --rows stream (context mode, M = 8, K = 256, --chunk rows per
@@ -15,7 +18,8 @@ produce the same bits.
   search   IVF.search at the same points beside the sum of its three parts
 
     python tools/bench_ivf.py [--rows 1000000] [--layout-rows 125000000] [--chunk 4]
-                              [--reps 20] [--ghz 2.4] [--out FILE.json]
+                              [--reps 20] [--pairs 3] [--ghz 2.4] [--only-assign]
+                              [--out FILE.json]
 """
 import argparse
 import json
@@ -58,8 +62,38 @@ def torch_assign(x, c, step=262_144):
                       for i in range(0, x.shape[0], step)])
 
 
+def screen_point(cq, x, reps, pairs):
+    """method="direct" and method="screen" in alternation on one quantizer and one set of rows"""
+    n = x.shape[0]
+    out = [torch.empty(n, dtype=torch.int32, device=x.device) for _ in range(2)]
+    dist = [torch.empty(n, device=x.device) for _ in range(2)]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    cq.assign(x, out=out[1], method="screen")   # builds the prepared centroids
+    e1.record()
+    torch.cuda.synchronize()
+    first = e0.elapsed_time(e1)
+    ms = {"direct": [], "screen": []}
+    for _ in range(pairs):
+        for i, method in enumerate(("direct", "screen")):
+            ms[method].append(timed(lambda: cq.assign(x, out=out[i], method=method), reps))
+    reranked, fallback = cq.screen_counts()
+    for i, method in enumerate(("direct", "screen")):
+        cq.assign(x, out=out[i], dist=dist[i], method=method)
+    same = bool(torch.equal(out[0], out[1]) and
+                torch.equal(dist[0].view(torch.int32), dist[1].view(torch.int32)))
+    best = {k: min(v) for k, v in ms.items()}
+    return {"direct_ms": ms["direct"], "screen_ms": ms["screen"],
+            "ratio_of_best": best["direct"] / best["screen"],
+            "first_screen_call_ms": first, "image_build_ms": first - best["screen"],
+            "reranked": reranked, "fallback": fallback, "list_and_dist_bits_equal": same}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--only-assign", action="store_true")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--layout-rows", type=int, default=125_000_000)
     ap.add_argument("--reps", type=int, default=20)
@@ -96,6 +130,23 @@ def main():
               f"({100 * ops / (t * 1e-3) / lanes_per_s:.1f} % of 256 x 128 lanes at {a.ghz} GHz, "
               f"clock not measured)  torch matmul + argmin {t_torch:.3f} ms  "
               f"(same list for {100 * agree:.2f} % of the rows)", flush=True)
+        gauss = torch.randn(n, d, device=dev, generator=torch.Generator(device=dev).manual_seed(9))
+        for name, rows in (("bench", x), ("gauss", gauss)):
+            cs = cq if rows is x else codec.Coarse(ctx, rows[:nlist].cpu().numpy())
+            p = screen_point(cs, rows, a.reps, a.pairs)
+            res["assign"][-1]["screen_" + name] = p
+            print(f"  {name} rows: direct {min(p['direct_ms']):.3f} ms  screen "
+                  f"{min(p['screen_ms']):.3f} ms  ratio {p['ratio_of_best']:.2f}  reranked "
+                  f"{p['reranked']}  fallback {p['fallback']}  image {p['image_build_ms']:.3f} ms  "
+                  f"equal bits {p['list_and_dist_bits_equal']}", flush=True)
+        del gauss
+    if a.only_assign:
+        if a.out:
+            with open(a.out, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+        print(json.dumps(res), flush=True)
+        return
 
     # ---- layout
     res["layout"] = []
