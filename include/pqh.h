@@ -106,7 +106,13 @@ int pqh_pq_destroy(pqh_pq_t* pq);
  * order, first minimum wins (oracle definition).  x rows are ld_x floats apart.
  * d_counts (optional, may be NULL): uint32 [m][k] non-context histogram accumulated
  * (+=) from the produced codes (huffman_encoder.c:139-164) -- fused in the kernel.
- * mode: 0 = MFMA screening + exact re-rank (default), 1 = exact VALU kernel only.
+ * mode: 0 = MFMA screening + exact re-rank (default), 1 = exact VALU kernel only,
+ * 2 = the LDS-resident screen: any K and any dsub <= 128 through a bf16-split MFMA screen over
+ * the sub-codebook held in LDS (streamed through it where it does not fit) with an exact finish
+ * in the same kernel; the codes, and d_counts, are mode 1's bit for bit for every input, NaN
+ * and infinities included; rows need no alignment.  The first mode-2 call of a codebook builds
+ * its prepared image on that call's stream (pqh_pq_destroy frees it); d_counts is served for
+ * every K in both layouts; dsub > 128 runs the exact kernel.
  * ctx: any context of the codebook's device; the launch uses its stream and scratch, so
  * contexts on different streams may assign concurrently. */
 int pqh_pq_assign(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_x, long long n,
@@ -123,6 +129,13 @@ int pqh_pq_assign_parts(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_x, lo
 /* diagnostics of the last pqh_pq_assign (synchronises): vectors x parts re-ranked
  * exactly because the screening could not separate the best two centroids. */
 int pqh_pq_last_rerank_count(pqh_ctx_t* ctx, unsigned long long* count);
+/* diagnostics of the last mode-2 assignment with rows on this context (synchronises), in
+ * (row, subspace) pairs: those whose screen kept more than one candidate, and those that took
+ * the chain over all K codes (a full candidate list, a non-finite value, scores that may
+ * overflow).  (0, 0) where the exact kernel ran (dsub > 128).  pqh_pq_last_rerank_count after
+ * such a call returns their sum. */
+int pqh_pq_last_screen_counts(pqh_ctx_t* ctx, unsigned long long* reranked,
+                              unsigned long long* fallback);
 
 /* mean squared reconstruction error (pq_encoder.c:82-119); synchronises. */
 int pqh_pq_error(pqh_ctx_t* ctx, const pqh_pq_t* pq, const float* d_x, long long n,
@@ -139,6 +152,11 @@ int pqh_pq_reconstruct(pqh_ctx_t* ctx, const pqh_pq_t* pq, const void* d_codes, 
  * d_x rows are ld_x floats apart (subspace i = columns [i*dsub, (i+1)*dsub)).  Synchronous. */
 int pqh_kmeans_train(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int m,
                      int k, int dsub, int iters, float* centroids);
+/* pqh_kmeans_train with its assignment through pqh_pq_assign's `assign_mode` (0: what
+ * pqh_kmeans_train runs).  The modes give equal codes and the sums are exact integers, so the
+ * centroids are the same bits in every mode. */
+int pqh_kmeans_train_mode(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int m,
+                          int k, int dsub, int iters, float* centroids, int assign_mode);
 
 /* ---- symbol histograms (huffman_encoder.c:139-205) ------------------------------- */
 /* counts += histogram of codes.  context: pairs (codes[v-1][i], codes[v][i]) for v >= 1,

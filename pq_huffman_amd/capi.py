@@ -124,9 +124,11 @@ SIGNATURES = [
     ("pqh_pq_assign", I, [P, P, P, LL, LL, P, P, I]),
     ("pqh_pq_assign_parts", I, [P, P, P, LL, LL, P, LL, P, I]),
     ("pqh_pq_last_rerank_count", I, [P, P]),
+    ("pqh_pq_last_screen_counts", I, [P, P, P]),
     ("pqh_pq_error", I, [P, P, P, LL, LL, P, P]),
     ("pqh_pq_reconstruct", I, [P, P, P, LL, P, LL]),
     ("pqh_kmeans_train", I, [P, P, LL, LL, I, I, I, I, P]),
+    ("pqh_kmeans_train_mode", I, [P, P, LL, LL, I, I, I, I, P, I]),
     ("pqh_histogram", I, [P, P, LL, I, I, I, P, P]),
     ("pqh_histogram_set", I, [P, P, LL, I, I, I, P, P]),
     ("pqh_histogram_parts", I, [P, P, LL, LL, I, I, I, P, P, I]),

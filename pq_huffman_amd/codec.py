@@ -179,10 +179,14 @@ class Context:
 class PQ:
     """Prepared sub-codebooks on the device (pq.h centroids_codebook_t + MFMA fragments)."""
 
-    def __init__(self, ctx: Context, centroids: np.ndarray):
+    def __init__(self, ctx: Context, centroids: np.ndarray, assign_mode: int = 0):
+        """assign_mode: the mode of assign / assign_parts calls that name none (pqh_pq_assign:
+        0 the MFMA kernel of its shapes, 1 the exact kernel, 2 the LDS-resident screen of any
+        shape); every user of the codebook -- IVF, refinement, OPQ training -- then takes it."""
         c = np.ascontiguousarray(centroids, np.float32)
         self.m, self.k, self.dsub = c.shape
         self.ctx = ctx
+        self.assign_mode = assign_mode
         self.ptr = ctypes.c_void_p()
         check(lib().pqh_pq_create(ctx.ptr, _ptr(c), self.m, self.k, self.dsub,
                                   ctypes.byref(self.ptr)), "pqh_pq_create")
@@ -193,7 +197,7 @@ class PQ:
         torch = _torch()
         return torch.uint8 if self.k <= 256 else torch.int16
 
-    def assign(self, x, codes=None, counts=None, mode: int = 0, ctx: Context = None):
+    def assign(self, x, codes=None, counts=None, mode: int = None, ctx: Context = None):
         """codes (n, m) of x; on `ctx`'s stream (any context of the same device, default the
         one the codebook was prepared with)."""
         torch = _torch()
@@ -202,10 +206,11 @@ class PQ:
             codes = torch.empty((n, self.m), dtype=self.code_dtype, device=x.device)
         c = ctx or self.ctx
         check(lib().pqh_pq_assign(c.ptr, self.ptr, _ptr(x), n, x.stride(0), _ptr(codes),
-                                  _ptr(counts), mode), "pqh_pq_assign")
+                                  _ptr(counts), self.assign_mode if mode is None else mode),
+              "pqh_pq_assign")
         return codes
 
-    def assign_parts(self, x, parts=None, counts=None, mode: int = 0, ctx: Context = None):
+    def assign_parts(self, x, parts=None, counts=None, mode: int = None, ctx: Context = None):
         """codes of x PART-MAJOR: parts (m, >= n), part i's codes contiguous in parts[i]
         (pqh_pq_assign_parts: the kernel stores whole lines)."""
         torch = _torch()
@@ -215,7 +220,8 @@ class PQ:
                                 device=x.device)[:, :n]
         c = ctx or self.ctx
         check(lib().pqh_pq_assign_parts(c.ptr, self.ptr, _ptr(x), n, x.stride(0), _ptr(parts),
-                                        parts.stride(0), _ptr(counts), mode),
+                                        parts.stride(0), _ptr(counts),
+                                        self.assign_mode if mode is None else mode),
               "pqh_pq_assign_parts")
         return parts
 
@@ -223,6 +229,14 @@ class PQ:
         v = ctypes.c_ulonglong(0)
         check(lib().pqh_pq_last_rerank_count((ctx or self.ctx).ptr, ctypes.byref(v)))
         return v.value
+
+    def screen_counts(self, ctx: Context = None):
+        """(reranked, fallback) of the last mode-2 assignment with rows on the context, in
+        (row, subspace) pairs (pqh_pq_last_screen_counts; synchronises)"""
+        a, b = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        check(lib().pqh_pq_last_screen_counts((ctx or self.ctx).ptr, ctypes.byref(a),
+                                              ctypes.byref(b)), "pqh_pq_last_screen_counts")
+        return a.value, b.value
 
     def error(self, x, codes) -> float:
         v = ctypes.c_double(0)
@@ -251,13 +265,14 @@ class PQ:
             pass
 
 
-def kmeans_train(ctx: Context, x, init: np.ndarray, iters: int) -> np.ndarray:
-    """Lloyd k-means of every subspace on the GPU (pqh_kmeans_train): exact assignment and
-    fixed-point centroid means, deterministic; init [m][k][dsub] -> trained centroids."""
+def kmeans_train(ctx: Context, x, init: np.ndarray, iters: int, mode: int = 0) -> np.ndarray:
+    """Lloyd k-means of every subspace on the GPU (pqh_kmeans_train_mode): exact assignment
+    (through pqh_pq_assign's `mode`; the same centroids in every mode) and fixed-point centroid
+    means, deterministic; init [m][k][dsub] -> trained centroids."""
     cent = np.ascontiguousarray(init, np.float32).copy()
     m, k, ds = cent.shape
-    check(lib().pqh_kmeans_train(ctx.ptr, _ptr(x), x.shape[0], x.stride(0), m, k, ds, iters,
-                                 _ptr(cent)), "pqh_kmeans_train")
+    check(lib().pqh_kmeans_train_mode(ctx.ptr, _ptr(x), x.shape[0], x.stride(0), m, k, ds, iters,
+                                      _ptr(cent), mode), "pqh_kmeans_train_mode")
     return cent
 
 
@@ -1335,7 +1350,7 @@ def pca_rotation(ctx: Context, x, m: int) -> np.ndarray:
 
 
 def opq_train(ctx: Context, x, m: int, k: int, cent_init: np.ndarray, outer: int = 8,
-              inner: int = 2, init="identity", trace: list = None):
+              inner: int = 2, init="identity", trace: list = None, assign_mode: int = 0):
     """(R, centroids, errors): a rotation and the product quantizer of the rotated rows, trained
     together (OPQ, the non-parametric form).  x: device float32 (n, d), d a multiple of m.
 
@@ -1360,7 +1375,8 @@ def opq_train(ctx: Context, x, m: int, k: int, cent_init: np.ndarray, outer: int
     +5 % on deep-like rows), "pca" (pca_rotation: for data with a spectrum -- 320 and 0.85 on
     that world, but 12 % behind the plain PQ on SIFT-like rows), or a (d, d) matrix.
     trace: a list that takes dict(R, cent, err, M) of every round (M: the moments the next R
-    came from, None for the last).  Synchronous."""
+    came from, None for the last).  assign_mode: pqh_pq_assign's mode for the inner k-means and
+    the codes (the same result in every mode).  Synchronous."""
     torch = _torch()
     n, d = x.shape
     cent = np.ascontiguousarray(cent_init, np.float32)
@@ -1383,8 +1399,8 @@ def opq_train(ctx: Context, x, m: int, k: int, cent_init: np.ndarray, outer: int
         rot = Rotation(ctx, R)
         rot.apply(x, out=xr)
         rot.close()
-        cent = kmeans_train(ctx, xr, cent, inner)
-        pq = PQ(ctx, cent)
+        cent = kmeans_train(ctx, xr, cent, inner, assign_mode)
+        pq = PQ(ctx, cent, assign_mode)
         try:
             codes = pq.assign(xr)
             errors.append(pq.error(xr, codes))

@@ -1766,6 +1766,7 @@ struct pqh_pq {
     float* d_cn = nullptr;     // ||c||^2 in accumulator order, [m][tile][half][16]
     float* d_cmax = nullptr;
     float* d_sqc = nullptr;
+    void* d_screen = nullptr;  // the image of mode 2 (pqh_assign_screen.hip), built by its first call
 };
 
 int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_cent) {
@@ -2004,6 +2005,7 @@ int pqh_pq_destroy(pqh_pq_t* pq) {
     (void)hipFree(pq->d_cn);
     (void)hipFree(pq->d_cmax);
     (void)hipFree(pq->d_sqc);
+    pqh_assign_screen_free(pq->d_screen);
     delete pq;
     return PQH_OK;
 }
@@ -2021,6 +2023,18 @@ static int assign_impl(pqh_ctx_t* ctx, const pqh_pq_t* cpq, const float* d_x, lo
         return PQH_ERR_ARG;
     int rc = pqh_use_device(ctx);
     if (rc) return rc;
+    if (mode == 2) {   // the LDS-resident screen, any shape; above its dsub the exact kernel
+        if (n == 0) return PQH_OK;
+        rc = pqh_assign_screen_clear(ctx);
+        if (rc) return rc;
+        if (pqh_assign_screen_serves(pq->dsub))
+            return pqh_assign_screen_launch(ctx, pq->m, pq->k, pq->dsub, pq->d_cent, &pq->d_screen,
+                                            d_x, n, ld_x, d_codes, ldc, d_counts);
+        return pq->k <= 256 ? launch_exact(ctx, pq, d_x, n, ld_x, static_cast<uint8_t*>(d_codes),
+                                           d_counts, ldc)
+                            : launch_exact(ctx, pq, d_x, n, ld_x, static_cast<uint16_t*>(d_codes),
+                                           d_counts, ldc);
+    }
     bool mfma = mode == 0 && pq->mfma_ok && n > 0;
     if (mfma && pq->dsub % 4 == 0 &&
         ((ld_x % 4) != 0 || (reinterpret_cast<uintptr_t>(d_x) & 15u) != 0))
@@ -2091,6 +2105,12 @@ int pqh_debug_assign_rr(pqh_ctx_t* ctx, unsigned long long* out, int max_waves) 
 
 int pqh_pq_last_rerank_count(pqh_ctx_t* ctx, unsigned long long* count) {
     if (!ctx || !count) return PQH_ERR_ARG;
+    if (ctx->rerank_slot == 11) {   // a mode-2 call: its re-ranked and its all-codes pairs
+        unsigned long long fallback = 0;
+        const int rc = pqh_pq_last_screen_counts(ctx, count, &fallback);
+        *count += fallback;
+        return rc;
+    }
     PQH_HIP(ctx, hipMemcpyAsync(count, ctx->d_diag + ctx->rerank_slot, sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, ctx->stream));
     PQH_HIP(ctx, hipStreamSynchronize(ctx->stream));

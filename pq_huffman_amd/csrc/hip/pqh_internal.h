@@ -31,7 +31,8 @@ struct pqh_ctx {
     // [0] / [4] re-rank counters of alternate assignment launches, [1] decode error,
     // [2] encode capacity error, [3] scratch total bits, [6] re-rank count of the exact path,
     // [5] sink of pqh_debug_poison_lds, [7] tree-order id error, [8] bad value met by
-    // pqh_ivf_layout / pqh_coarse_probe (sticky until pqh_ivf_status); kDiagSlots words
+    // pqh_ivf_layout / pqh_coarse_probe (sticky until pqh_ivf_status), [9] / [10] the coarse
+    // screen's counts, [11] / [12] the PQ screen's; kDiagSlots words
     unsigned long long* d_diag = nullptr;
     // one-pass encoder look-back state: [lb_cap] block states, [lb_cap] tails, ticket
     unsigned long long* lb_state = nullptr;
@@ -91,6 +92,16 @@ int pqh_pq_error_accum(pqh_ctx* ctx, const pqh_pq_t* pq, const float* d_x, long 
 // a prepared codebook's shape and its device centroids [m][k][dsub] (pqh_assign.hip), for the
 // fused reconstruction of pqh_fetch_vectors; PQH_ERR_ARG for a null codebook
 int pqh_pq_view(const pqh_pq_t* pq, int* m, int* k, int* dsub, const float** d_cent);
+// the screened PQ assignment (pqh_assign_screen.hip), mode 2 of pqh_pq_assign: whether it serves
+// a dsub; the clearing of its two d_diag counts (which pqh_pq_last_rerank_count then sums); the
+// launch over n > 0 rows, which builds *image on its first call for a codebook, on the context's
+// stream; and the release of an image (null: nothing)
+bool pqh_assign_screen_serves(int dsub);
+int pqh_assign_screen_clear(pqh_ctx* ctx);
+int pqh_assign_screen_launch(pqh_ctx* ctx, int m, int k, int dsub, const float* d_cent, void** image,
+                             const float* d_x, long long n, long long ld_x, void* d_codes,
+                             long long ldc, uint32_t* d_counts);
+void pqh_assign_screen_free(void* image);
 // the coarse quantizer (pqh_ivf.hip)
 struct pqh_coarse {
     pqh_ctx* ctx = nullptr;

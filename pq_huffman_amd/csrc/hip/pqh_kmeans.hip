@@ -135,6 +135,11 @@ extern "C" {
 
 int pqh_kmeans_train(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int m,
                      int k, int dsub, int iters, float* centroids) {
+    return pqh_kmeans_train_mode(ctx, d_x, n, ld_x, m, k, dsub, iters, centroids, 0);
+}
+
+int pqh_kmeans_train_mode(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int m,
+                          int k, int dsub, int iters, float* centroids, int assign_mode) {
     if (!ctx || !centroids || m <= 0 || k <= 0 || dsub <= 0 || iters < 0 || n < 0 ||
         (n > 0 && !d_x) || ld_x < (long long)m * dsub)
         return PQH_ERR_ARG;
@@ -184,7 +189,7 @@ int pqh_kmeans_train(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld
     for (int it = 0; it < iters; ++it) {
         pqh_pq_t* pq = nullptr;
         rc = pqh_pq_create(ctx, centroids, m, k, dsub, &pq);
-        if (!rc) rc = pqh_pq_assign(ctx, pq, d_x, n, ld_x, d_codes, nullptr, 0);
+        if (!rc) rc = pqh_pq_assign(ctx, pq, d_x, n, ld_x, d_codes, nullptr, assign_mode);
         if (pq) pqh_pq_destroy(pq);
         if (rc) {
             cleanup();
