@@ -1219,6 +1219,53 @@ int pqh_shard_search_merge(pqh_ctx_t* ctx, const pqh_shard_comm_t* comm,
  * failed. */
 int pqh_shard_search_status(pqh_ctx_t* ctx, const long long* d_state);
 
+/* ---- flat search: the exact top-k over raw fp32 rows --------------------------------------
+ * For query q and row v, dist is the direct-form fp32 chain of pqh_coarse_assign with the query
+ * as the left operand: L2  t = q[j] - x[v][j]; acc = acc + t * t;  inner product
+ * acc = acc - q[j] * x[v][j] (the negated inner product); j ascending from +0.0f, no
+ * contraction.  The result per query is the k smallest by (dist, id) ascending, id = id_base + v,
+ * padded with (+inf, -1); bits and order do not depend on the grid.  For finite inputs whose
+ * chains stay finite it is what pqh_coarse_probe / _ip return over the same rows, dist bit for
+ * bit.  The chain is run only for the pairs a bf16-split matrix-instruction screen cannot rule
+ * out (d <= 1,024; above it for every pair), by a bound that is proven, so the result is the
+ * definition's, not an approximation.  Non-finite inputs give unspecified results; nothing is
+ * read or written out of bounds and every call terminates.
+ * Conventions of the search calls: device pointers, asynchronous on the context's stream, a NULL
+ * context answered first (PQH_ERR_NO_DEVICE when no HIP device is visible, else PQH_ERR_ARG).
+ *
+ * pqh_flat_create: the object REFERS to the caller's rows d_x [n] (ld_x >= d floats apart, the
+ * floats between rows never read) and makes no copy: the caller keeps them alive and unchanged
+ * until pqh_flat_destroy.  It owns 4 bytes per row, ||x_v||^2 summed in double and rounded once,
+ * and their maximum, built by one pass on the context's stream.  0 <= n <= 2^31 - 1 (more:
+ * PQH_ERR_UNSUPPORTED), d >= 1, else PQH_ERR_ARG; d_x may be NULL when n == 0.
+ * pqh_flat_destroy synchronises the stream of the context the object was made with. */
+typedef struct pqh_flat pqh_flat_t;
+int pqh_flat_create(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
+                    pqh_flat_t** flat);
+int pqh_flat_destroy(pqh_flat_t* flat);
+/* d_dist float [nq][k], d_ids int64 [nq][k].  Queries ld_q >= d floats apart.  d_keep_bits (may
+ * be NULL): the row mask of the *_masked searches (bit v & 31 of word v >> 5, ceil(n / 32)
+ * words, 4-byte aligned); only rows whose bit is set take part, and the result is the top k of
+ * those.  1 <= k <= the context's limit (PQH_SEARCH_MAX_K, or what pqh_ctx_set_search_max_k set,
+ * 256 at the most); ctx is the context the object was made with (its norms are written on that
+ * context's stream); 0 <= id_base <= 2^63 - 1 - n; else PQH_ERR_ARG, as for a null pointer with
+ * nq > 0, nq < 0, ld_q < d or a misaligned mask.  nq >= 2^31: PQH_ERR_UNSUPPORTED.  nq == 0
+ * launches nothing, n == 0 only the padding fill.  Workspace: 12 * slabs * nq * k bytes of the
+ * context's scratch when the rows are cut into more than one slab (at most one slab per compute
+ * unit, 1,024 rows at least), freed by pqh_ctx_release_scratch. */
+int pqh_flat_search(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_queries, long long nq,
+                    long long ld_q, int k, const unsigned int* d_keep_bits /* or NULL */,
+                    long long id_base, float* d_dist, long long* d_ids);
+int pqh_flat_search_ip(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_queries,
+                       long long nq, long long ld_q, int k,
+                       const unsigned int* d_keep_bits /* or NULL */, long long id_base,
+                       float* d_dist, long long* d_ids);
+/* Synchronises: of the last flat search on this context that had work (nq > 0 and n > 0), the
+ * number of (query, row) pairs whose exact chain was run, and the number of queries that took
+ * the all-rows path (a non-finite query or row, a scale at which a score can overflow; every
+ * query when d > 1,024). */
+int pqh_flat_last_counts(pqh_ctx_t* ctx, unsigned long long* chains, unsigned long long* fallback);
+
 /* Host: (this rank's global bit offset, the global length) from every rank's bit length. */
 int pqh_shard_offsets(const unsigned long long* lengths, int world, int rank,
                       unsigned long long* offset, unsigned long long* total);

@@ -246,6 +246,11 @@ SIGNATURES = [
     ("pqh_shard_search_scratch_bytes", ULL, [I, LL, I]),
     ("pqh_shard_search_merge", I, [P, P, P, P, LL, I, LL, I, P, ULL, P, P, P]),
     ("pqh_shard_search_status", I, [P, P]),
+    # the flat (exact) search over raw rows
+    ("pqh_flat_create", I, [P, P, LL, LL, I, P]), ("pqh_flat_destroy", I, [P]),
+    ("pqh_flat_search", I, [P, P, P, LL, LL, I, P, LL, P, P]),
+    ("pqh_flat_search_ip", I, [P, P, P, LL, LL, I, P, LL, P, P]),
+    ("pqh_flat_last_counts", I, [P, P, P]),
     ("pqh_shard_offsets", I, [P, I, I, P, P]),
     ("pqh_shard_stitch", I, [I, P, P, P, P, ULL]),
     ("pqh_shard_halo_source", I, [P, I, I, P, P]),

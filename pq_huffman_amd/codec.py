@@ -1239,6 +1239,88 @@ class Coarse:
             pass
 
 
+def _rows_ok(t, d: int) -> bool:
+    """t is a device float32 tensor of shape (rows, >= d) whose columns are one float apart"""
+    if t.dim() != 2 or t.dtype != _torch().float32 or t.shape[1] < d:
+        return False
+    # (a tensor without elements is never read: its strides and device do not matter)
+    return t.numel() == 0 or (t.is_cuda and (t.shape[1] == 1 or t.stride(1) == 1))
+
+
+class Flat:
+    """The exact search over raw rows (pqh_flat_t): x device float32 (n, >= d), which the object
+    holds and refers to -- no copy is made, so x must not change while the object is in use.
+    d: the dimensions searched (default: every column of x).  It owns 4 bytes per row (the
+    squared norms of the screen).  Distances are the direct form in fp32, query first, ties go
+    to the smaller id: what Coarse(ctx, x).probe returns over the same rows, bit for bit."""
+
+    def __init__(self, ctx: Context, x, d: int = None):
+        torch = _torch()
+        if not _rows_ok(x, 1):
+            raise PqhError(-1, "Flat: x is a device float32 tensor of shape (n, >= d) with unit column stride")
+        self.ctx, self.x = ctx, x
+        self.n, self.d = x.shape[0], int(x.shape[1] if d is None else d)
+        if not 1 <= self.d <= x.shape[1]:
+            raise PqhError(-1, f"Flat: d = {self.d} of {x.shape[1]} columns")
+        self.ptr = ctypes.c_void_p()
+        check(lib().pqh_flat_create(ctx.ptr, _ptr(x) if self.n else None, self.n, _ld(x, self.d),
+                                    self.d, ctypes.byref(self.ptr)), "pqh_flat_create")
+        ctx._retain()
+
+    def search(self, queries, k: int, metric: str = "l2", keep=None, id_base: int = 0, out=None):
+        """(dist, ids), each (nq, k): for every query (device float32 (nq, >= d)) the k rows
+        nearest by (dist, id), ids = rows + id_base, padded with (+inf, -1) (pqh_flat_search).
+        metric="ip": the rows of the largest inner products, dist their negations
+        (pqh_flat_search_ip).  keep: a device bool tensor over the rows, or the packed int32 words
+        of pack_mask; only kept rows take part.  k <= ctx.search_max_k.  Async."""
+        torch = _torch()
+        name = "pqh_flat_search" + _metric_suffix(metric, "Flat.search")
+        if not _rows_ok(queries, self.d) or (queries.numel() and self.x.numel() and
+                                             queries.device != self.x.device):
+            raise PqhError(-1, "Flat.search: queries is a float32 tensor of shape (nq, >= d) with "
+                               "unit column stride on the device of x")
+        nq = queries.shape[0]
+        if out is not None and not (
+                out[0].dtype == torch.float32 and out[1].dtype == torch.int64 and
+                all(t.shape == (nq, k) and t.is_contiguous() and t.device == self.x.device
+                    for t in out)):
+            raise PqhError(-1, "Flat.search: out is a contiguous (float32, int64) pair of shape (nq, k) on the device of x")
+        if keep is not None and keep.dtype in (torch.bool, torch.uint8):
+            if keep.numel() != self.n:
+                raise PqhError(-1, f"Flat.search: {keep.numel()} keep flags for {self.n} rows")
+            keep = pack_mask(self.ctx, keep)
+        if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
+                                 keep.numel() < (self.n + 31) // 32):
+            raise PqhError(-1, "Flat.search: keep is bool (n,) or contiguous int32 ceil(n / 32) words")
+        if out is None:
+            out = (torch.empty((nq, k), dtype=torch.float32, device=queries.device),
+                   torch.empty((nq, k), dtype=torch.int64, device=queries.device))
+        check(getattr(lib(), name)(self.ctx.ptr, self.ptr, _ptr(queries), nq, _ld(queries, self.d),
+                                   k, _ptr(keep), id_base, _ptr(out[0]), _ptr(out[1])), name)
+        return out
+
+    def counts(self):
+        """(chains, fallback) of the context's last flat search that had work: the (query, row)
+        pairs whose exact chain was run, and the queries that took the all-rows path.  Waits."""
+        a, b = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(lib().pqh_flat_last_counts(self.ctx.ptr, ctypes.byref(a), ctypes.byref(b)),
+              "pqh_flat_last_counts")
+        return a.value, b.value
+
+    def close(self):
+        if self.ptr:
+            lib().pqh_flat_destroy(self.ptr)
+            self.ptr = ctypes.c_void_p()
+            self.x = None
+            self.ctx._release()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _ld(t, d: int) -> int:
     """the floats between two rows of t; a tensor of fewer than two rows has no such distance
     (torch reports 0 for an empty one), and any value >= d serves"""

@@ -32,7 +32,7 @@ struct pqh_ctx {
     // [2] encode capacity error, [3] scratch total bits, [6] re-rank count of the exact path,
     // [5] sink of pqh_debug_poison_lds, [7] tree-order id error, [8] bad value met by
     // pqh_ivf_layout / pqh_coarse_probe (sticky until pqh_ivf_status), [9] / [10] the coarse
-    // screen's counts, [11] / [12] the PQ screen's; kDiagSlots words
+    // screen's counts, [11] / [12] the PQ screen's, [13] / [14] the flat search's; kDiagSlots words
     unsigned long long* d_diag = nullptr;
     // one-pass encoder look-back state: [lb_cap] block states, [lb_cap] tails, ticket
     unsigned long long* lb_state = nullptr;
