@@ -1266,6 +1266,46 @@ int pqh_flat_search_ip(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_qu
  * query when d > 1,024). */
 int pqh_flat_last_counts(pqh_ctx_t* ctx, unsigned long long* chains, unsigned long long* fallback);
 
+/* ---- IVF-Flat: the exact top-k over the raw rows of probed lists ---------------------------
+ * pqh_flat_search's distances and order, restricted per query to the rows of the lists it
+ * probes: d_x are the rows IN LIST ORDER (ld_x >= d floats apart, the floats between rows never
+ * read), list l the rows [d_offsets[l], d_offsets[l + 1]), d_offsets int64 [nlist + 1] and
+ * d_probes int64 [nq][nprobe] (-1 = none) as pqh_ivf_layout and pqh_coarse_probe write them.
+ * Every distance is the definition's chain, so the result is exact by construction and any
+ * d >= 1 is served.  The result per query is the top_k smallest by (dist, row) among the kept
+ * rows of its probed lists, ids = id_base + row of d_x, padded with (+inf, -1); bits and order
+ * depend on neither the grid nor the order of the probes.  A list that appears twice in a
+ * query's probes offers its rows twice, as in pqh_search_codes_lists, and a row can then be
+ * returned twice; a probe of -1 and a list without rows contribute nothing.
+ * d_keep_bits (may be NULL): the row mask of the *_masked searches over the rows of d_x
+ * (ceil(n / 32) words, 4-byte aligned); a tile of 256 rows without a kept row is not read.
+ * The probes are turned round on the device as in pqh_search_stream_lists, into work units of a
+ * list and up to 16 of its pairs (4 when top_k > 64).
+ * Checked before the context is looked at, PQH_ERR_ARG: n < 0, d < 1, ld_x < d, ld_q < d,
+ * nlist < 1, nq < 0, nprobe outside [1, PQH_IVF_MAX_NPROBE], top_k outside
+ * [1, PQH_SEARCH_MAX_K_WIDE], id_base outside [0, 2^63 - 1 - n], a misaligned mask, and with
+ * nq > 0 a null d_offsets, d_probes, d_queries, d_dist, d_ids or (n > 0) d_x.  Then a NULL
+ * context is answered as in the search calls, and top_k above the context's limit is
+ * PQH_ERR_ARG.  PQH_ERR_UNSUPPORTED: n, nlist or nq * nprobe >= 2^31.  nq == 0 launches nothing,
+ * n == 0 only the padding fill.  Bad device data -- a probe below -1 or >= nlist, a probed list
+ * whose offsets are not 0 <= d_offsets[l] <= d_offsets[l + 1] <= n -- contributes no rows, reads
+ * nothing out of bounds and makes pqh_ivf_status answer PQH_ERR_ARG.  Asynchronous on the
+ * context's stream.  Scratch (the context's workspace): 12 bytes * nq * nprobe * G * top_k for
+ * G groups a unit (1 unless lists are long or units few, 64 at the most; the context's
+ * search_groups tuning sets it), and the plan of pqh_search_stream_lists. */
+int pqh_flat_search_lists(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
+                          const long long* d_offsets /* [nlist + 1] */, long long nlist,
+                          const long long* d_probes /* [nq][nprobe], -1 = none */,
+                          const float* d_queries, long long nq, long long ld_q, int nprobe,
+                          int top_k, const unsigned int* d_keep_bits /* or NULL */,
+                          long long id_base, float* d_dist, long long* d_ids);
+int pqh_flat_search_lists_ip(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
+                             const long long* d_offsets, long long nlist,
+                             const long long* d_probes, const float* d_queries, long long nq,
+                             long long ld_q, int nprobe, int top_k,
+                             const unsigned int* d_keep_bits, long long id_base, float* d_dist,
+                             long long* d_ids);
+
 /* Host: (this rank's global bit offset, the global length) from every rank's bit length. */
 int pqh_shard_offsets(const unsigned long long* lengths, int world, int rank,
                       unsigned long long* offset, unsigned long long* total);

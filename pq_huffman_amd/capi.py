@@ -251,6 +251,10 @@ SIGNATURES = [
     ("pqh_flat_search", I, [P, P, P, LL, LL, I, P, LL, P, P]),
     ("pqh_flat_search_ip", I, [P, P, P, LL, LL, I, P, LL, P, P]),
     ("pqh_flat_last_counts", I, [P, P, P]),
+    # IVF-Flat: x, n, ld_x, d, offsets, nlist, probes, queries, nq, ld_q, nprobe, top_k, keep,
+    # id_base, dist, ids
+    ("pqh_flat_search_lists", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
+    ("pqh_flat_search_lists_ip", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
     ("pqh_shard_offsets", I, [P, I, I, P, P]),
     ("pqh_shard_stitch", I, [I, P, P, P, P, ULL]),
     ("pqh_shard_halo_source", I, [P, I, I, P, P]),

@@ -1327,6 +1327,110 @@ def _ld(t, d: int) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), d)
 
 
+def flat_search_lists(ctx: Context, x_sorted, offsets, probes, queries, k: int, metric: str = "l2",
+                      keep=None, id_base: int = 0, d: int = None):
+    """(dist, rows), each (nq, k): for every query (device float32 (nq, >= d)) the k nearest by
+    (dist, row) among the rows of the lists it probes, by the exact distances of Flat.search
+    (pqh_flat_search_lists, _ip for metric="ip").  x_sorted: device float32 (n, >= d), the rows
+    in list order; offsets: device int64 (nlist + 1,), list l at rows [offsets[l],
+    offsets[l + 1]); probes: device int64 (nq, nprobe), -1 = none, as Coarse.probe gives them.
+    rows = rows of x_sorted + id_base, padded with (+inf, -1).  keep: a device bool tensor over
+    the rows of x_sorted, or the packed int32 words of pack_mask.  d: the dimensions searched
+    (default: every column of x_sorted).  k <= ctx.search_max_k.  Async; ivf_status reports a
+    probe outside [-1, nlist) or a bad offsets pair of a probed list (the probe skipped)."""
+    torch = _torch()
+    name = "pqh_flat_search_lists" + _metric_suffix(metric, "flat_search_lists")
+    if not _rows_ok(x_sorted, 1):
+        raise PqhError(-1, "flat_search_lists: x_sorted is a device float32 tensor of shape (n, >= d) "
+                           "with unit column stride")
+    n, d = x_sorted.shape[0], int(x_sorted.shape[1] if d is None else d)
+    if not 1 <= d <= x_sorted.shape[1]:
+        raise PqhError(-1, f"flat_search_lists: d = {d} of {x_sorted.shape[1]} columns")
+    if not _rows_ok(queries, d) or (queries.numel() and x_sorted.numel() and
+                                    queries.device != x_sorted.device):
+        raise PqhError(-1, "flat_search_lists: queries is a float32 tensor of shape (nq, >= d) with "
+                           "unit column stride on the device of x_sorted")
+    nq = queries.shape[0]
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise PqhError(-1, "flat_search_lists: probes is an int64 tensor of shape (nq, nprobe)")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous():
+        raise PqhError(-1, "flat_search_lists: offsets is a contiguous int64 tensor of shape (nlist + 1,)")
+    if not probes.is_contiguous():
+        probes = probes.contiguous()
+    if keep is not None and keep.dtype in (torch.bool, torch.uint8):
+        if keep.numel() != n:
+            raise PqhError(-1, f"flat_search_lists: {keep.numel()} keep flags for {n} rows")
+        keep = pack_mask(ctx, keep)
+    if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
+                             keep.numel() < (n + 31) // 32):
+        raise PqhError(-1, "flat_search_lists: keep is bool (n,) or contiguous int32 ceil(n / 32) words")
+    dist = torch.empty((nq, k), dtype=torch.float32, device=probes.device)
+    rows = torch.empty((nq, k), dtype=torch.int64, device=probes.device)
+    check(getattr(lib(), name)(ctx.ptr, _ptr(x_sorted) if n else None, n, _ld(x_sorted, d), d,
+                               _ptr(offsets), offsets.numel() - 1, _ptr(probes), _ptr(queries), nq,
+                               _ld(queries, d), probes.shape[1], k, _ptr(keep), id_base,
+                               _ptr(dist), _ptr(rows)), name)
+    return dist, rows
+
+
+class IVFFlat:
+    """An inverted file over raw rows: the exact distances of Flat, but only over the rows of the
+    lists a query probes -- the recall ceiling the coarse quantizer sets for an IVF of the same
+    lists.  It owns x_sorted (its own copy of the rows, list by list), perm (row of x_sorted ->
+    row of x), offsets and metric; the quantizer is the caller's."""
+
+    def __init__(self, ctx: Context, coarse: "Coarse", x_sorted, perm, offsets, metric: str):
+        self.ctx, self.coarse, self.metric = ctx, coarse, metric
+        self.x_sorted, self.perm, self.offsets = x_sorted, perm, offsets
+        self.n = x_sorted.shape[0]
+        self.live = None          # bool per row of x_sorted once remove() was called
+        self._live_words = None
+
+    @classmethod
+    def build(cls, ctx: Context, coarse: "Coarse", x, metric: str = "l2", assign: str = "direct"):
+        """the index of the rows x (device float32 (n, >= coarse.d)): coarse.assign(metric=,
+        method=assign), coarse.layout, and one gather of the rows into list order.  Async."""
+        _metric_suffix(metric, "IVFFlat.build")
+        if not _rows_ok(x, coarse.d):
+            raise PqhError(-1, "IVFFlat.build: x is a device float32 tensor of shape (n, >= d) with "
+                               "unit column stride")
+        perm, offsets = coarse.layout(coarse.assign(x, metric=metric, method=assign))
+        return cls(ctx, coarse, x[:, :coarse.d][perm].contiguous(), perm, offsets, metric)
+
+    def remove(self, ids) -> None:
+        """take the rows `ids` of x (device int64, each in [0, n)) out of every later search:
+        tombstones, as IVF.remove; the rows stay in place.  Removing a row twice is harmless."""
+        torch = _torch()
+        if self.live is None:
+            self.live = torch.ones(self.n, dtype=torch.bool, device=self.perm.device)
+            self._inv = torch.empty_like(self.perm)
+            self._inv[self.perm] = torch.arange(self.n, dtype=torch.int64, device=self.perm.device)
+        self.live[self._inv[ids.reshape(-1)]] = False
+        self._live_words = pack_mask(self.ctx, self.live)
+
+    def live_count(self) -> int:
+        """the rows remove() has left (synchronises once a row was removed)"""
+        return self.n if self.live is None else int(self.live.sum().item())
+
+    def search(self, queries, nprobe: int, k: int, keep=None):
+        """(dist, ids), each (nq, k): the k nearest rows by exact distance among the rows of each
+        query's nprobe nearest lists (coarse.probe(metric=), then flat_search_lists); ids are rows
+        of x, padded with (+inf, -1).  keep: device bool (n,) over the rows of x.  Rows taken out
+        by remove() are never returned.  Async."""
+        torch = _torch()
+        mask = self._live_words
+        if keep is not None:
+            if keep.dtype != torch.bool or keep.shape != (self.n,):
+                raise PqhError(-1, "IVFFlat.search: keep is a bool tensor of shape (n,)")
+            mask = pack_mask(self.ctx, keep, self.perm)
+            if self._live_words is not None:
+                mask = mask & self._live_words
+        _, _, probes, _ = self.coarse.probe(queries, nprobe, self.offsets, metric=self.metric)
+        dist, rows = flat_search_lists(self.ctx, self.x_sorted, self.offsets, probes, queries, k,
+                                       metric=self.metric, keep=mask)
+        return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
+
+
 class Rotation:
     """A d x d matrix on the device (pqh_rotation_t), applied to rows before the quantizers see
     them: the learned rotation of OPQ.  R: host float32 (d, d), 1 <= d <= 1024.  Any matrix is

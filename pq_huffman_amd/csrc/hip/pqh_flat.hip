@@ -36,6 +36,7 @@
 #include <new>
 #include <type_traits>
 
+#include "pqh_flat_dev.h"
 #include "pqh_internal.h"
 #include "pqh_screen_dev.h"
 #include "pqh_topk_dev.h"
@@ -104,17 +105,6 @@ flat_norms(const float* __restrict__ x, long long n, long long ld_x, int d,
     if ((threadIdx.x & 63) == 0 && bits) atomicMax(cmax, bits);
 }
 
-// ------------------------------------------------------------------- the definition's chain
-template <bool IP>
-__device__ __forceinline__ void chain_step(float& acc, float qv, float xv) {
-    if constexpr (IP) {
-        acc = acc - qv * xv;
-    } else {
-        const float t = qv - xv;
-        acc = acc + t * t;
-    }
-}
-
 // U independent chains of one lane, interleaved (a chain alone is a string of dependent
 // operations); vec: every row on 16 bytes and d % 4 == 0
 template <bool IP, int U>
@@ -145,56 +135,6 @@ __device__ __forceinline__ void chains(const float* const (&qp)[U], const float*
 #pragma unroll
             for (int u = 0; u < U; ++u) chain_step<IP>(out[u], qp[u][j], xp[u][j]);
         }
-    }
-}
-
-// ------------------------------------------------------------------- a query's list
-template <int KR>
-using ListT = std::conditional_t<KR == 1, TopK, TopKW>;
-
-template <int KR>
-__device__ __forceinline__ void list_reset(ListT<KR>& e) {
-    if constexpr (KR == 1) {
-        e.d = INFINITY;
-        e.id = -1ll;
-    } else {
-        list_clear(e);
-    }
-}
-
-template <int KR>
-__device__ __forceinline__ float list_kth(const ListT<KR>& e, int kth) {
-    if constexpr (KR == 1) {
-        return lane_f(e.d, kth);
-    } else {
-        return e.td;
-    }
-}
-
-// the k entries of a list in LDS (dist, row of the slab) into the lanes, padding behind them
-template <int KR>
-__device__ __forceinline__ void list_from_lds(ListT<KR>& e, const float* ld, const int* li, int k) {
-    const int lane = threadIdx.x;
-    list_reset<KR>(e);
-    if constexpr (KR == 1) {
-        if (lane < k) e.d = ld[lane], e.id = (long long)li[lane];
-    } else {
-#pragma unroll
-        for (int b = 0; b < kWideKR; ++b)
-            if (b * 64 + lane < k) e.d[b] = ld[b * 64 + lane], e.id[b] = (long long)li[b * 64 + lane];
-        list_threshold(e, k - 1);
-    }
-}
-
-template <int KR>
-__device__ __forceinline__ void list_to_lds(const ListT<KR>& e, float* ld, int* li, int k) {
-    const int lane = threadIdx.x;
-    if constexpr (KR == 1) {
-        if (lane < k) ld[lane] = e.d, li[lane] = (int)e.id;
-    } else {
-#pragma unroll
-        for (int b = 0; b < kWideKR; ++b)
-            if (b * 64 + lane < k) ld[b * 64 + lane] = e.d[b], li[b * 64 + lane] = (int)e.id[b];
     }
 }
 

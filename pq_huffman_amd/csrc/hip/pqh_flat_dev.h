@@ -1,0 +1,76 @@
+// pqh_flat_dev.h -- what the exact searches over raw rows share (pqh_flat.hip, the screen over all
+// rows, and pqh_flat_lists.hip, the direct scan of probed lists): one step of the definition's
+// chain, and a query's running list kept in LDS between the offers that change it.  Device code
+// only; every list function is called by a whole wave whose lane number is threadIdx.x.
+#pragma once
+
+#include <cmath>
+#include <type_traits>
+
+#include "pqh_internal.h"
+#include "pqh_topk_dev.h"
+
+namespace {
+
+// ------------------------------------------------------------------- the definition's chain
+template <bool IP>
+__device__ __forceinline__ void chain_step(float& acc, float qv, float xv) {
+    if constexpr (IP) {
+        acc = acc - qv * xv;
+    } else {
+        const float t = qv - xv;
+        acc = acc + t * t;
+    }
+}
+
+// ------------------------------------------------------------------- a query's list
+template <int KR>
+using ListT = std::conditional_t<KR == 1, TopK, TopKW>;
+
+template <int KR>
+__device__ __forceinline__ void list_reset(ListT<KR>& e) {
+    if constexpr (KR == 1) {
+        e.d = INFINITY;
+        e.id = -1ll;
+    } else {
+        list_clear(e);
+    }
+}
+
+template <int KR>
+__device__ __forceinline__ float list_kth(const ListT<KR>& e, int kth) {
+    if constexpr (KR == 1) {
+        return lane_f(e.d, kth);
+    } else {
+        return e.td;
+    }
+}
+
+// the k entries of a list in LDS (dist, row of the slab) into the lanes, padding behind them
+template <int KR>
+__device__ __forceinline__ void list_from_lds(ListT<KR>& e, const float* ld, const int* li, int k) {
+    const int lane = threadIdx.x;
+    list_reset<KR>(e);
+    if constexpr (KR == 1) {
+        if (lane < k) e.d = ld[lane], e.id = (long long)li[lane];
+    } else {
+#pragma unroll
+        for (int b = 0; b < kWideKR; ++b)
+            if (b * 64 + lane < k) e.d[b] = ld[b * 64 + lane], e.id[b] = (long long)li[b * 64 + lane];
+        list_threshold(e, k - 1);
+    }
+}
+
+template <int KR>
+__device__ __forceinline__ void list_to_lds(const ListT<KR>& e, float* ld, int* li, int k) {
+    const int lane = threadIdx.x;
+    if constexpr (KR == 1) {
+        if (lane < k) ld[lane] = e.d, li[lane] = (int)e.id;
+    } else {
+#pragma unroll
+        for (int b = 0; b < kWideKR; ++b)
+            if (b * 64 + lane < k) ld[b * 64 + lane] = e.d[b], li[b * 64 + lane] = (int)e.id[b];
+    }
+}
+
+}  // namespace

@@ -115,6 +115,33 @@ struct pqh_coarse {
 // a coarse quantizer's shape and its device centroids [nlist][d] (pqh_ivf.hip), for the re-rank
 // of a residual index (pqh_refine.hip); PQH_ERR_ARG for a null quantizer
 int pqh_coarse_view(const pqh_coarse_t* cq, int* nlist, int* d, const float** d_cent);
+// The list-major plan of the probe searches (pqh_search.hip: lists_zero / count / plan / fill),
+// for the searches of other files that scan probed lists (pqh_flat_lists.hip).  In: the probe
+// list, qb pairs a unit at the most, pad = a pair's entries of the partial lists (a pair without
+// a unit gets the padding there), units_bound = min(npairs, nlist + npairs / qb), and mem,
+// pqh_list_plan_bytes(...) bytes of device memory on 8 bytes.  Out: the units [bound][3] (list,
+// first entry of pairs, entries), their count, and the pairs list by list.  Error bit 2 into *err.
+struct pqh_list_plan {
+    const long long* offsets;
+    long long nlist;
+    const long long* probes;
+    long long npairs, n;
+    int qb;
+    long long pad, units_bound;
+    void* mem;
+    float* part_d;
+    long long* part_id;
+    unsigned long long* err;
+    const long long* units;
+    const long long* nunits;
+    const int* pairs;
+};
+size_t pqh_list_plan_bytes(long long nlist, long long npairs, long long units_bound);
+int pqh_list_plan_launch(pqh_ctx* ctx, pqh_list_plan* p);
+// adc_merge / adc_merge_wide over partial lists [nq][lists][top_k] (lists = 0: the padding alone)
+int pqh_lists_merge_launch(pqh_ctx* ctx, const float* part_d, const long long* part_id,
+                           long long lists, long long nq, int top_k, long long id_base,
+                           float* d_dist, long long* d_ids);
 // pqh_shard_encode's histogram / size / write with this shard's raw-first flag in device
 // memory (1: row 0 raw, no halo pair; 0: row 0 in the context of d_prev_row) -- pqh_huff.hip
 extern "C" {

@@ -604,6 +604,52 @@ int merge_launch(pqh_ctx_t* ctx, const float* pd, const long long* pid, long lon
     return PQH_OK;
 }
 
+}  // namespace
+
+// the plan's memory: the units [bound][3] and their count, the lists' counts, the pairs
+size_t pqh_list_plan_bytes(long long nlist, long long npairs, long long units_bound) {
+    return ((size_t)units_bound * 3 + 1) * 8 + (((size_t)nlist * 4 + 7) & ~(size_t)7) +
+           (size_t)npairs * 4;
+}
+
+int pqh_list_plan_launch(pqh_ctx* ctx, pqh_list_plan* p) {
+    long long* units = static_cast<long long*>(p->mem);
+    ListArgs la{};
+    la.offsets = p->offsets;
+    la.nlist = p->nlist;
+    la.probes = p->probes;
+    la.npairs = p->npairs;
+    la.n = p->n;
+    la.qb = p->qb;
+    la.pad = p->pad;
+    la.units = units;
+    la.nunits = units + p->units_bound * 3;
+    la.cnt = reinterpret_cast<int*>(la.nunits + 1);
+    la.pairs = reinterpret_cast<int*>(reinterpret_cast<char*>(la.cnt) +
+                                      (((size_t)p->nlist * 4 + 7) & ~(size_t)7));
+    la.part_d = p->part_d;
+    la.part_id = p->part_id;
+    la.err = p->err;
+    const dim3 by_list((unsigned)((p->nlist + 255) / 256)), by_pair((unsigned)((p->npairs + 255) / 256));
+    hipLaunchKernelGGL(lists_zero, by_list, dim3(256), 0, ctx->stream, la);
+    hipLaunchKernelGGL(lists_count, by_pair, dim3(256), 0, ctx->stream, la);
+    hipLaunchKernelGGL(lists_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, la);
+    hipLaunchKernelGGL(lists_fill, by_pair, dim3(256), 0, ctx->stream, la);
+    PQH_LAUNCH_CHECK(ctx);
+    p->units = la.units;
+    p->nunits = la.nunits;
+    p->pairs = la.pairs;
+    return PQH_OK;
+}
+
+int pqh_lists_merge_launch(pqh_ctx* ctx, const float* part_d, const long long* part_id,
+                           long long lists, long long nq, int top_k, long long id_base,
+                           float* d_dist, long long* d_ids) {
+    return merge_launch(ctx, part_d, part_id, lists, nq, top_k, id_base, d_dist, d_ids);
+}
+
+namespace {
+
 // the scan and the merge; a.C, a.n, a.m, a.k and the source are set by the caller, nw = the
 // row's u64 words (0: per part).  rg: the probe search (a.range_ptr, a.ranges and a.nr set):
 // the plan first, then one query per workgroup.  rt (with rg): a.lut holds one table per
@@ -659,9 +705,8 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
     const size_t entries = (size_t)a.nq * lists * a.top_k;
     // beside the partial lists -- rg: the plan; ls: the units [batches][3] and their count,
     // the lists' counts and the pairs
-    const size_t cnt_bytes = ls ? (((size_t)ls->nlist * 4 + 7) & ~(size_t)7) : 0;
     const size_t plan_bytes = rg   ? ((size_t)a.nr + 1) * 8
-                              : ls ? ((size_t)batches * 3 + 1) * 8 + cnt_bytes + (size_t)npairs * 4
+                              : ls ? pqh_list_plan_bytes(ls->nlist, npairs, batches)
                                    : 0;
     rc = pqh_ensure_ws(ctx, entries * 12 + 16 + plan_bytes);
     if (rc) return rc;
@@ -676,31 +721,24 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, ScanArgs a, long long 
         a.plan = plan;
     }
     if (ls) {
-        long long* units = static_cast<long long*>(ctx->ws) + ((entries * 12 + 15) / 8);
-        ListArgs la{};
-        la.offsets = ls->offsets;
-        la.nlist = ls->nlist;
-        la.probes = ls->probes;
-        la.npairs = npairs;
-        la.n = a.n;
-        la.qb = qb;
-        la.pad = groups * a.top_k;
-        la.units = units;
-        la.nunits = units + batches * 3;
-        la.cnt = reinterpret_cast<int*>(la.nunits + 1);
-        la.pairs = reinterpret_cast<int*>(reinterpret_cast<char*>(la.cnt) + cnt_bytes);
-        la.part_d = a.part_d;
-        la.part_id = a.part_id;
-        la.err = a.err;
-        const dim3 by_list((unsigned)((ls->nlist + 255) / 256)), by_pair((unsigned)((npairs + 255) / 256));
-        hipLaunchKernelGGL(lists_zero, by_list, dim3(256), 0, ctx->stream, la);
-        hipLaunchKernelGGL(lists_count, by_pair, dim3(256), 0, ctx->stream, la);
-        hipLaunchKernelGGL(lists_plan, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, la);
-        hipLaunchKernelGGL(lists_fill, by_pair, dim3(256), 0, ctx->stream, la);
-        PQH_LAUNCH_CHECK(ctx);
-        a.units = la.units;
-        a.nunits = la.nunits;
-        a.pairs = la.pairs;
+        pqh_list_plan lp{};
+        lp.offsets = ls->offsets;
+        lp.nlist = ls->nlist;
+        lp.probes = ls->probes;
+        lp.npairs = npairs;
+        lp.n = a.n;
+        lp.qb = qb;
+        lp.pad = groups * a.top_k;
+        lp.units_bound = batches;
+        lp.mem = static_cast<long long*>(ctx->ws) + ((entries * 12 + 15) / 8);
+        lp.part_d = a.part_d;
+        lp.part_id = a.part_id;
+        lp.err = a.err;
+        rc = pqh_list_plan_launch(ctx, &lp);
+        if (rc) return rc;
+        a.units = lp.units;
+        a.nunits = lp.nunits;
+        a.pairs = lp.pairs;
     }
     // (the end of the kernel exchanges the waves' lists, 12 bytes an entry, through the same LDS)
     const size_t lds =
