@@ -1306,6 +1306,76 @@ int pqh_flat_search_lists_ip(pqh_ctx_t* ctx, const float* d_x, long long n, long
                              const unsigned int* d_keep_bits, long long id_base, float* d_dist,
                              long long* d_ids);
 
+/* ---- IVF-SQ8: rows as 8-bit codes of a scalar quantizer per dimension ------------------------
+ * d bytes a row, and the exact top-k over the DECODED rows of probed lists.  There is no object:
+ * the quantizer is two device arrays of the caller's, float vmin[d] and step[d].
+ * The definition.  fp32 throughout, every operation rounds once, no fused multiply-add; the
+ * division is the correctly rounded fp32 division.
+ *   train   over the finite values of column j, lo their minimum and hi their maximum (by the
+ *           order of the values with -0 below +0): vmin[j] = lo, step[j] = fl(fl(hi - lo) / 255.0f).
+ *           A column without a finite value gets (0, 0).  A range hi - lo that overflows fp32 is
+ *           out of scope: step is then +inf, every code 0 and every decoded value NaN.
+ *   encode  t = fl(fl(x_j - vmin[j]) / step[j]); code = 0 if t is NaN, else
+ *           min(255, max(0, rint(t))), ties to even.  A constant column (step = 0) therefore
+ *           codes to 0 (x_j = vmin[j], or NaN, or below) or 255 and decodes to vmin either way.
+ *   decode  dec_j = fl(vmin[j] + fl((float)code * step[j])).
+ *   search  pqh_flat_search_lists's chain with dec in the place of the row, j ascending:
+ *           L2  t = q_j - dec_j, acc = acc + t * t;   inner product  acc = acc - q_j * dec_j.
+ * So a search equals pqh_flat_search_lists over the rows pqh_sq_decode writes, ids and the bits
+ * of dist, and decoded rows coincide often: the order (dist, row) decides among them.
+ * Conventions: device pointers, asynchronous on the context's stream; the argument checks come
+ * before the context is looked at, a NULL context is then answered as in the search calls.
+ * d_codes are rows of d bytes, ld_c >= d bytes apart, n * ld_c bytes that may all be READ (the
+ * bytes from d to ld_c of a row are never used, and the encoder leaves them alone).
+ *
+ * pqh_sq_train: vmin and step from the rows d_x [n] (ld_x >= d floats apart).  n == 0: (0, 0)
+ * everywhere.  Scratch: 8 * d bytes of the context's workspace (the order-preserving keys of the
+ * minima and maxima, merged by integer atomics: the result does not depend on the grid).
+ * PQH_ERR_ARG: n < 0, d < 1, ld_x < d, a null d_vmin or d_step, a null d_x with n > 0.
+ * pqh_sq_encode: d_codes[s] = the codes of row d_perm[s] of d_x (d_perm NULL: row s), n rows in
+ * and out, so the rows can go into list order in the same pass (d_perm int64 [n] as
+ * pqh_ivf_layout writes it).  A d_perm entry outside [0, n) gives a row of zero codes and makes
+ * pqh_ivf_status answer PQH_ERR_ARG.  No scratch.  Fast paths: float4 reads where d % 4 == 0,
+ * ld_x % 4 == 0 and d_x, d_vmin, d_step lie on 16 bytes; four codes as one dword store where
+ * ld_c % 4 == 0 and d_codes lies on 4 bytes.  PQH_ERR_ARG: n < 0, d < 1, ld_x < d, ld_c < d,
+ * with n > 0 a null d_x, d_vmin, d_step or d_codes; PQH_ERR_UNSUPPORTED: n * ceil(d / 4) >= 2^39.
+ * pqh_sq_decode: d_out[i] (count rows, ld_out >= d floats apart, the floats from d on left
+ * alone) = the decoded row d_rows[i], or with d_rows NULL the row first + i.  d_rows[i] == -1
+ * gives a row of zeros; an entry below -1 or >= n too, and pqh_ivf_status then answers
+ * PQH_ERR_ARG.  No scratch.  Fast paths: four codes as one dword read as above; float4 stores
+ * where d % 4 == 0, ld_out % 4 == 0 and d_out lies on 16 bytes.  PQH_ERR_ARG: n < 0, d < 1,
+ * ld_c < d, ld_out < d, count < 0, with d_rows NULL a range outside [0, n], with count > 0 a
+ * null d_out, d_vmin, d_step or (n > 0) d_codes; PQH_ERR_UNSUPPORTED as for the encoder.
+ * pqh_sq_search_lists / _ip: pqh_flat_search_lists with d_codes, ld_c in the place of d_x, ld_x
+ * and the quantizer behind d: the same result contract (rows in list order, offsets, probes,
+ * mask, id_base, padding, duplicates), the same checks in the same order with ld_c < d for
+ * ld_x < d and a null d_vmin or d_step counted with a null d_codes, the same
+ * PQH_ERR_UNSUPPORTED limits, the same report of bad device data through pqh_ivf_status, the
+ * same scratch (12 bytes * nq * nprobe * G * top_k and the plan).  Fast path: a row's chunk of
+ * 64 bytes is read 16 bytes a lane where ld_c % 4 == 0 and d_codes lies on 4 bytes (a lane's
+ * 16 bytes that cross d are read by dwords); else byte by byte. */
+int pqh_sq_train(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
+                 float* d_vmin, float* d_step);
+int pqh_sq_encode(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
+                  const long long* d_perm /* or NULL */, const float* d_vmin, const float* d_step,
+                  unsigned char* d_codes, long long ld_c);
+int pqh_sq_decode(pqh_ctx_t* ctx, const unsigned char* d_codes, long long n, long long ld_c, int d,
+                  const float* d_vmin, const float* d_step, const long long* d_rows /* or NULL */,
+                  long long first, long long count, float* d_out, long long ld_out);
+int pqh_sq_search_lists(pqh_ctx_t* ctx, const unsigned char* d_codes, long long n, long long ld_c,
+                        int d, const float* d_vmin, const float* d_step,
+                        const long long* d_offsets /* [nlist + 1] */, long long nlist,
+                        const long long* d_probes /* [nq][nprobe], -1 = none */,
+                        const float* d_queries, long long nq, long long ld_q, int nprobe,
+                        int top_k, const unsigned int* d_keep_bits /* or NULL */,
+                        long long id_base, float* d_dist, long long* d_ids);
+int pqh_sq_search_lists_ip(pqh_ctx_t* ctx, const unsigned char* d_codes, long long n,
+                           long long ld_c, int d, const float* d_vmin, const float* d_step,
+                           const long long* d_offsets, long long nlist, const long long* d_probes,
+                           const float* d_queries, long long nq, long long ld_q, int nprobe,
+                           int top_k, const unsigned int* d_keep_bits, long long id_base,
+                           float* d_dist, long long* d_ids);
+
 /* Host: (this rank's global bit offset, the global length) from every rank's bit length. */
 int pqh_shard_offsets(const unsigned long long* lengths, int world, int rank,
                       unsigned long long* offset, unsigned long long* total);

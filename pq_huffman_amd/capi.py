@@ -255,6 +255,14 @@ SIGNATURES = [
     # id_base, dist, ids
     ("pqh_flat_search_lists", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
     ("pqh_flat_search_lists_ip", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
+    # IVF-SQ8.  train: x, n, ld_x, d, vmin, step; encode: x, n, ld_x, d, perm, vmin, step, codes,
+    # ld_c; decode: codes, n, ld_c, d, vmin, step, rows, first, count, out, ld_out; the searches:
+    # codes, n, ld_c, d, vmin, step, then pqh_flat_search_lists's from offsets on
+    ("pqh_sq_train", I, [P, P, LL, LL, I, P, P]),
+    ("pqh_sq_encode", I, [P, P, LL, LL, I, P, P, P, P, LL]),
+    ("pqh_sq_decode", I, [P, P, LL, LL, I, P, P, P, LL, LL, P, LL]),
+    ("pqh_sq_search_lists", I, [P, P, LL, LL, I, P, P, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
+    ("pqh_sq_search_lists_ip", I, [P, P, LL, LL, I, P, P, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
     ("pqh_shard_offsets", I, [P, I, I, P, P]),
     ("pqh_shard_stitch", I, [I, P, P, P, P, ULL]),
     ("pqh_shard_halo_source", I, [P, I, I, P, P]),

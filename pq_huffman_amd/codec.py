@@ -1385,6 +1385,14 @@ class IVFFlat:
         self.n = x_sorted.shape[0]
         self.live = None          # bool per row of x_sorted once remove() was called
         self._live_words = None
+        self._inv = None          # row of x -> row of x_sorted, once it was asked for
+
+    def _inverse(self):
+        torch = _torch()
+        if self._inv is None:
+            self._inv = torch.empty_like(self.perm)
+            self._inv[self.perm] = torch.arange(self.n, dtype=torch.int64, device=self.perm.device)
+        return self._inv
 
     @classmethod
     def build(cls, ctx: Context, coarse: "Coarse", x, metric: str = "l2", assign: str = "direct"):
@@ -1403,9 +1411,7 @@ class IVFFlat:
         torch = _torch()
         if self.live is None:
             self.live = torch.ones(self.n, dtype=torch.bool, device=self.perm.device)
-            self._inv = torch.empty_like(self.perm)
-            self._inv[self.perm] = torch.arange(self.n, dtype=torch.int64, device=self.perm.device)
-        self.live[self._inv[ids.reshape(-1)]] = False
+        self.live[self._inverse()[ids.reshape(-1)]] = False
         self._live_words = pack_mask(self.ctx, self.live)
 
     def live_count(self) -> int:
@@ -1426,9 +1432,161 @@ class IVFFlat:
             if self._live_words is not None:
                 mask = mask & self._live_words
         _, _, probes, _ = self.coarse.probe(queries, nprobe, self.offsets, metric=self.metric)
-        dist, rows = flat_search_lists(self.ctx, self.x_sorted, self.offsets, probes, queries, k,
-                                       metric=self.metric, keep=mask)
+        dist, rows = self._scan(probes, queries, k, mask)
         return dist, torch.where(rows >= 0, self.perm[rows.clamp(min=0)], rows)
+
+    def _scan(self, probes, queries, k, mask):
+        return flat_search_lists(self.ctx, self.x_sorted, self.offsets, probes, queries, k,
+                                 metric=self.metric, keep=mask)
+
+
+class SQ:
+    """An 8-bit scalar quantizer per dimension (pqh.h, IVF-SQ8): vmin and step, device float32
+    (d,), which the object holds.  code = rint((x - vmin) / step) clamped to [0, 255],
+    dec = vmin + code * step, every operation one fp32 rounding."""
+
+    def __init__(self, ctx: Context, vmin, step):
+        torch = _torch()
+        if not all(t.dtype == torch.float32 and t.dim() == 1 and t.is_cuda and t.is_contiguous()
+                   for t in (vmin, step)) or vmin.shape != step.shape or vmin.numel() < 1:
+            raise PqhError(-1, "SQ: vmin and step are contiguous device float32 tensors of shape (d,)")
+        self.ctx, self.vmin, self.step, self.d = ctx, vmin, step, vmin.numel()
+
+    @classmethod
+    def train(cls, ctx: Context, x):
+        """the quantizer of the rows x (device float32 (n, d)): per column the minimum of its
+        finite values and a 255th of their range (pqh_sq_train).  Async."""
+        torch = _torch()
+        if not _rows_ok(x, 1) or not x.is_cuda:
+            raise PqhError(-1, "SQ.train: x is a device float32 tensor of shape (n, d) with unit column stride")
+        d = x.shape[1]
+        vmin, step = (torch.empty(d, dtype=torch.float32, device=x.device) for _ in range(2))
+        check(lib().pqh_sq_train(ctx.ptr, _ptr(x) if x.shape[0] else None, x.shape[0], _ld(x, d), d,
+                                 _ptr(vmin), _ptr(step)), "pqh_sq_train")
+        return cls(ctx, vmin, step)
+
+    def encode(self, x, perm=None, ld: int = None):
+        """uint8 (n, ld): row s the codes of row perm[s] of x (perm None: row s) in its first d
+        bytes, zeros behind them (pqh_sq_encode).  x: device float32 (n, >= d); perm: device
+        int64 (n,) as Coarse.layout returns it; ld >= d, by default d rounded up to 4 (the fast
+        paths of the scan).  Async; ivf_status reports a perm entry outside [0, n)."""
+        torch = _torch()
+        if not _rows_ok(x, self.d):
+            raise PqhError(-1, "SQ.encode: x is a device float32 tensor of shape (n, >= d) with unit column stride")
+        n, ld = x.shape[0], (self.d + 3) // 4 * 4 if ld is None else int(ld)
+        if ld < self.d or (perm is not None and (perm.dtype != torch.int64 or perm.shape != (n,))):
+            raise PqhError(-1, "SQ.encode: ld >= d, and perm is an int64 tensor of shape (n,)")
+        if perm is not None and not perm.is_contiguous():
+            perm = perm.contiguous()
+        codes = torch.zeros((n, ld), dtype=torch.uint8, device=self.vmin.device)
+        check(lib().pqh_sq_encode(self.ctx.ptr, _ptr(x) if n else None, n, _ld(x, self.d), self.d,
+                                  _ptr(perm), _ptr(self.vmin), _ptr(self.step), _ptr(codes), ld),
+              "pqh_sq_encode")
+        return codes
+
+    def _codes_ok(self, codes) -> bool:
+        return (codes.dim() == 2 and codes.dtype == _torch().uint8 and codes.shape[1] >= self.d and
+                (codes.numel() == 0 or (codes.is_cuda and (codes.shape[1] == 1 or codes.stride(1) == 1))))
+
+    def decode(self, codes, rows=None):
+        """float32 (count, d): the decoded rows `rows` of codes (device int64 (count,), -1 = a
+        row of zeros), or every row (pqh_sq_decode).  codes: device uint8 (n, >= d) as encode
+        returns them.  Async; ivf_status reports a row below -1 or >= n (zeros)."""
+        torch = _torch()
+        if not self._codes_ok(codes):
+            raise PqhError(-1, "SQ.decode: codes is a device uint8 tensor of shape (n, >= d) with unit column stride")
+        if rows is not None and (rows.dtype != torch.int64 or rows.dim() != 1):
+            raise PqhError(-1, "SQ.decode: rows is an int64 tensor of shape (count,)")
+        if rows is not None and not rows.is_contiguous():
+            rows = rows.contiguous()
+        n = codes.shape[0]
+        count = n if rows is None else rows.numel()
+        out = torch.empty((count, self.d), dtype=torch.float32, device=self.vmin.device)
+        check(lib().pqh_sq_decode(self.ctx.ptr, _ptr(codes) if n else None, n, _ld(codes, self.d),
+                                  self.d, _ptr(self.vmin), _ptr(self.step), _ptr(rows), 0, count,
+                                  _ptr(out), self.d), "pqh_sq_decode")
+        return out
+
+
+def sq_search_lists(ctx: Context, sq: SQ, codes_sorted, offsets, probes, queries, k: int,
+                    metric: str = "l2", keep=None, id_base: int = 0):
+    """flat_search_lists over the rows sq.decode(codes_sorted) without decoding them to memory
+    (pqh_sq_search_lists, _ip for metric="ip"): the same distances, order, padding, mask and
+    reports, bit for bit.  codes_sorted: device uint8 (n, >= sq.d), the codes in list order."""
+    torch = _torch()
+    name = "pqh_sq_search_lists" + _metric_suffix(metric, "sq_search_lists")
+    if not sq._codes_ok(codes_sorted):
+        raise PqhError(-1, "sq_search_lists: codes_sorted is a device uint8 tensor of shape (n, >= d) "
+                           "with unit column stride")
+    n, d = codes_sorted.shape[0], sq.d
+    if not _rows_ok(queries, d) or (queries.numel() and queries.device != sq.vmin.device):
+        raise PqhError(-1, "sq_search_lists: queries is a float32 tensor of shape (nq, >= d) with "
+                           "unit column stride on the device of the quantizer")
+    nq = queries.shape[0]
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise PqhError(-1, "sq_search_lists: probes is an int64 tensor of shape (nq, nprobe)")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous():
+        raise PqhError(-1, "sq_search_lists: offsets is a contiguous int64 tensor of shape (nlist + 1,)")
+    if not probes.is_contiguous():
+        probes = probes.contiguous()
+    if keep is not None and keep.dtype in (torch.bool, torch.uint8):
+        if keep.numel() != n:
+            raise PqhError(-1, f"sq_search_lists: {keep.numel()} keep flags for {n} rows")
+        keep = pack_mask(ctx, keep)
+    if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
+                             keep.numel() < (n + 31) // 32):
+        raise PqhError(-1, "sq_search_lists: keep is bool (n,) or contiguous int32 ceil(n / 32) words")
+    dist = torch.empty((nq, k), dtype=torch.float32, device=probes.device)
+    rows = torch.empty((nq, k), dtype=torch.int64, device=probes.device)
+    check(getattr(lib(), name)(ctx.ptr, _ptr(codes_sorted) if n else None, n, _ld(codes_sorted, d), d,
+                               _ptr(sq.vmin), _ptr(sq.step), _ptr(offsets), offsets.numel() - 1,
+                               _ptr(probes), _ptr(queries), nq, _ld(queries, d), probes.shape[1], k,
+                               _ptr(keep), id_base, _ptr(dist), _ptr(rows)), name)
+    return dist, rows
+
+
+class IVFSQ(IVFFlat):
+    """IVFFlat over 8-bit codes: d bytes a row (rounded up to 4) where IVFFlat holds 4 d, and the
+    exact search over the decoded rows -- search() equals IVFFlat's over fetch(arange(n)).  It
+    owns codes (list by list), perm, offsets and metric; the quantizers are the caller's."""
+
+    def __init__(self, ctx: Context, coarse: "Coarse", sq: SQ, codes, perm, offsets, metric: str):
+        super().__init__(ctx, coarse, codes, perm, offsets, metric)
+        self.sq, self.codes, self.x_sorted = sq, codes, None
+
+    @classmethod
+    def build(cls, ctx: Context, coarse: "Coarse", x, sq: SQ = None, metric: str = "l2",
+              assign: str = "direct"):
+        """the index of the rows x (device float32 (n, >= coarse.d)): SQ.train on x when sq is
+        None, coarse.assign(metric=, method=assign), coarse.layout, and one encoding pass that
+        gathers the rows into list order.  Async."""
+        _metric_suffix(metric, "IVFSQ.build")
+        if not _rows_ok(x, coarse.d):
+            raise PqhError(-1, "IVFSQ.build: x is a device float32 tensor of shape (n, >= d) with "
+                               "unit column stride")
+        if sq is None:
+            sq = SQ.train(ctx, x[:, :coarse.d])
+        if sq.d != coarse.d:
+            raise PqhError(-1, f"IVFSQ.build: a quantizer of {sq.d} dimensions for {coarse.d}")
+        perm, offsets = coarse.layout(coarse.assign(x, metric=metric, method=assign))
+        return cls(ctx, coarse, sq, sq.encode(x, perm), perm, offsets, metric)
+
+    def _scan(self, probes, queries, k, mask):
+        return sq_search_lists(self.ctx, self.sq, self.codes, self.offsets, probes, queries, k,
+                               metric=self.metric, keep=mask)
+
+    def fetch(self, ids):
+        """float32 (count, d): the decoded rows `ids` of x (device int64, each in [-1, n)), -1 a
+        row of zeros.  Async."""
+        torch = _torch()
+        ids = ids.reshape(-1)
+        return self.sq.decode(self.codes, torch.where(ids >= 0, self._inverse()[ids.clamp(min=0)], ids))
+
+    def nbytes(self) -> int:
+        """the device bytes the index owns and the scalar quantizer's: codes, perm, offsets,
+        vmin and step"""
+        return sum(t.numel() * t.element_size()
+                   for t in (self.codes, self.perm, self.offsets, self.sq.vmin, self.sq.step))
 
 
 class Rotation:

@@ -1,7 +1,8 @@
 // pqh_flat_dev.h -- what the exact searches over raw rows share (pqh_flat.hip, the screen over all
 // rows, and pqh_flat_lists.hip, the direct scan of probed lists): one step of the definition's
-// chain, and a query's running list kept in LDS between the offers that change it.  Device code
-// only; every list function is called by a whole wave whose lane number is threadIdx.x.
+// chain, the rule for the groups of a list scan (host code, shared with pqh_sq.hip), and a
+// query's running list kept in LDS between the offers that change it.  Every list function is
+// device code, called by a whole wave whose lane number is threadIdx.x.
 #pragma once
 
 #include <cmath>
@@ -21,6 +22,26 @@ __device__ __forceinline__ void chain_step(float& acc, float qv, float xv) {
         const float t = qv - xv;
         acc = acc + t * t;
     }
+}
+
+// ------------------------------------------------------------------- the groups of a list scan
+// (host) The groups a unit of the list scans is cut into (flat_lists, sq_lists).  The lists'
+// lengths are device data, so the plan goes by the mean list: a group per kSegRows rows of it;
+// and where the units are fewer than the compute units, as many groups as fill them, two a tile
+// of the mean list at the most.  The context's search_groups tuning sets them outright.
+constexpr long long kSegRows = 2048;   // mean list length from which a unit is cut into groups
+constexpr int kMaxGroups = 64;
+inline long long lists_groups(const pqh_ctx* ctx, long long n, long long nlist, long long bound,
+                              int tile) {
+    const long long mean = (n + nlist - 1) / nlist;
+    long long groups = (mean + kSegRows - 1) / kSegRows;
+    if (bound * groups < ctx->num_cus) {
+        const long long fill = (ctx->num_cus + bound - 1) / bound, most = 2 * ((mean + tile - 1) / tile);
+        groups = fill < most ? fill : most;
+    }
+    groups = groups < 1 ? 1 : groups > kMaxGroups ? kMaxGroups : groups;
+    if (ctx->tune_search_groups > 0) groups = ctx->tune_search_groups < 65535 ? ctx->tune_search_groups : 65535;
+    return groups;
 }
 
 // ------------------------------------------------------------------- a query's list

@@ -41,8 +41,6 @@ constexpr int kJC = 32;             // dimensions a staged chunk
 constexpr int kPitch = kJC + 1;
 constexpr int kWaves = 4;
 constexpr int kPre = kTile * kJC / (64 * kWaves);   // floats of a chunk a thread moves: 32
-constexpr long long kSegRows = 2048;   // mean list length from which a unit is cut into groups
-constexpr int kMaxGroups = 64;
 
 struct ListsArgs {
     const float* x;
@@ -315,15 +313,7 @@ int search_lists(bool ip, pqh_ctx_t* ctx, const float* d_x, long long n, long lo
     const int qb = lists_qb(wide ? kWideKR : 1);
     const long long npairs = nq * nprobe;
     const long long bound = std::min<long long>(npairs, nlist + npairs / qb);
-    // The groups of a unit.  The lists' lengths are device data, so the plan goes by the mean
-    // list: a group per kSegRows rows of it; and where the units are fewer than the compute
-    // units, as many groups as fill them, two a tile of the mean list at the most.
-    const long long mean = (n + nlist - 1) / nlist;
-    long long groups = (mean + kSegRows - 1) / kSegRows;
-    if (bound * groups < ctx->num_cus)
-        groups = std::min<long long>((ctx->num_cus + bound - 1) / bound, 2 * ((mean + kTile - 1) / kTile));
-    groups = std::max<long long>(1, std::min<long long>(groups, kMaxGroups));
-    if (ctx->tune_search_groups > 0) groups = std::min(ctx->tune_search_groups, 65535);
+    const long long groups = lists_groups(ctx, n, nlist, bound, kTile);   // (pqh_flat_dev.h)
 
     const size_t entries = (size_t)npairs * groups * top_k;
     rc = pqh_ensure_ws(ctx, entries * 12 + 16 + pqh_list_plan_bytes(nlist, npairs, bound));
