@@ -1306,6 +1306,42 @@ int pqh_flat_search_lists_ip(pqh_ctx_t* ctx, const float* d_x, long long n, long
                              const unsigned int* d_keep_bits, long long id_base, float* d_dist,
                              long long* d_ids);
 
+/* ---- half-precision rows: the flat search and IVF-Flat over fp16 and bf16 storage ------------
+ * The *_rows calls take the rows' element type.  Every fp16 and bf16 value is exactly an fp32
+ * value, so a search over 16-bit rows IS the fp32 search over the rows converted to fp32: the same
+ * ids and the same bits of dist, no tolerance.  The conversion is exact (fp16 subnormals are not
+ * flushed); non-finite rows behave as in the fp32 calls.  Queries, distances and everything else
+ * stay fp32.
+ * d_x lies on the element's size (4 bytes, or 2 for the 16-bit types) and ld_x >= d counts
+ * ELEMENTS; the elements from d to ld_x of a row are never used, whatever they hold.  An unknown
+ * `rows` or a d_x off its element size is PQH_ERR_ARG, answered first; every other check, status
+ * report, scratch, id_base, mask and padding rule is the one of the call without _rows, in its
+ * order.  PQH_ROWS_F32 forwards to that call and launches exactly what it launches.
+ * pqh_flat_create_rows: pqh_flat_create for rows of the type `rows`; the object knows its type,
+ * and pqh_flat_search / _ip, pqh_flat_last_counts and pqh_flat_destroy serve it unchanged.  The
+ * norms are double sums of the converted values; the screen, its threshold, the fallback rule
+ * and the counts are those of fp32 rows (bf16 rows need no low half, fp16 rows split exactly).
+ * pqh_flat_search_lists_rows / _ip: pqh_flat_search_lists / _ip with the rows' type after d_x.
+ * The 16-bit scan stages a tile as 16-bit values (two workgroups a compute unit where the fp32
+ * scan has one); 16-byte loads are taken where ld_x is even and d_x lies on 4 bytes. */
+#define PQH_ROWS_F32 0
+#define PQH_ROWS_F16 1
+#define PQH_ROWS_BF16 2
+int pqh_flat_create_rows(pqh_ctx_t* ctx, const void* d_x, int rows, long long n, long long ld_x,
+                         int d, pqh_flat_t** flat);
+int pqh_flat_search_lists_rows(pqh_ctx_t* ctx, const void* d_x, int rows, long long n,
+                               long long ld_x, int d, const long long* d_offsets, long long nlist,
+                               const long long* d_probes, const float* d_queries, long long nq,
+                               long long ld_q, int nprobe, int top_k,
+                               const unsigned int* d_keep_bits /* or NULL */, long long id_base,
+                               float* d_dist, long long* d_ids);
+int pqh_flat_search_lists_rows_ip(pqh_ctx_t* ctx, const void* d_x, int rows, long long n,
+                                  long long ld_x, int d, const long long* d_offsets,
+                                  long long nlist, const long long* d_probes,
+                                  const float* d_queries, long long nq, long long ld_q, int nprobe,
+                                  int top_k, const unsigned int* d_keep_bits, long long id_base,
+                                  float* d_dist, long long* d_ids);
+
 /* ---- IVF-SQ8: rows as 8-bit codes of a scalar quantizer per dimension ------------------------
  * d bytes a row, and the exact top-k over the DECODED rows of probed lists.  There is no object:
  * the quantizer is two device arrays of the caller's, float vmin[d] and step[d].

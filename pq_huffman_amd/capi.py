@@ -255,6 +255,10 @@ SIGNATURES = [
     # id_base, dist, ids
     ("pqh_flat_search_lists", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
     ("pqh_flat_search_lists_ip", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
+    # rows of a given element type (PQH_ROWS_F32 / F16 / BF16 after x): the calls above with it
+    ("pqh_flat_create_rows", I, [P, P, I, LL, LL, I, P]),
+    ("pqh_flat_search_lists_rows", I, [P, P, I, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
+    ("pqh_flat_search_lists_rows_ip", I, [P, P, I, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
     # IVF-SQ8.  train: x, n, ld_x, d, vmin, step; encode: x, n, ld_x, d, perm, vmin, step, codes,
     # ld_c; decode: codes, n, ld_c, d, vmin, step, rows, first, count, out, ld_out; the searches:
     # codes, n, ld_c, d, vmin, step, then pqh_flat_search_lists's from offsets on

@@ -1247,24 +1247,42 @@ def _rows_ok(t, d: int) -> bool:
     return t.numel() == 0 or (t.is_cuda and (t.shape[1] == 1 or t.stride(1) == 1))
 
 
+def _row_types():
+    """torch dtype -> PQH_ROWS_* of the stored rows, and the names IVFFlat.build(store=) takes"""
+    torch = _torch()
+    return ({torch.float32: 0, torch.float16: 1, torch.bfloat16: 2},
+            {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16})
+
+
+def _stored_ok(t, d: int) -> bool:
+    """_rows_ok for stored rows: float32, float16 or bfloat16"""
+    if t.dim() != 2 or t.dtype not in _row_types()[0] or t.shape[1] < d:
+        return False
+    return t.numel() == 0 or (t.is_cuda and (t.shape[1] == 1 or t.stride(1) == 1))
+
+
 class Flat:
-    """The exact search over raw rows (pqh_flat_t): x device float32 (n, >= d), which the object
-    holds and refers to -- no copy is made, so x must not change while the object is in use.
-    d: the dimensions searched (default: every column of x).  It owns 4 bytes per row (the
-    squared norms of the screen).  Distances are the direct form in fp32, query first, ties go
-    to the smaller id: what Coarse(ctx, x).probe returns over the same rows, bit for bit."""
+    """The exact search over raw rows (pqh_flat_t): x device float32, float16 or bfloat16
+    (n, >= d), which the object holds and refers to -- no copy is made, so x must not change
+    while the object is in use.  d: the dimensions searched (default: every column of x).  It
+    owns 4 bytes per row (the squared norms of the screen).  Distances are the direct form in
+    fp32, query first, ties go to the smaller id: what Coarse(ctx, x).probe returns over the same
+    rows, bit for bit.  Rows of a 16-bit type are searched as x.float() would be (every such
+    value is an fp32 value), without that copy; queries stay float32."""
 
     def __init__(self, ctx: Context, x, d: int = None):
         torch = _torch()
-        if not _rows_ok(x, 1):
-            raise PqhError(-1, "Flat: x is a device float32 tensor of shape (n, >= d) with unit column stride")
+        if not _stored_ok(x, 1):
+            raise PqhError(-1, "Flat: x is a device float32, float16 or bfloat16 tensor of shape "
+                               "(n, >= d) with unit column stride")
         self.ctx, self.x = ctx, x
         self.n, self.d = x.shape[0], int(x.shape[1] if d is None else d)
         if not 1 <= self.d <= x.shape[1]:
             raise PqhError(-1, f"Flat: d = {self.d} of {x.shape[1]} columns")
         self.ptr = ctypes.c_void_p()
-        check(lib().pqh_flat_create(ctx.ptr, _ptr(x) if self.n else None, self.n, _ld(x, self.d),
-                                    self.d, ctypes.byref(self.ptr)), "pqh_flat_create")
+        check(lib().pqh_flat_create_rows(ctx.ptr, _ptr(x) if self.n else None, _row_types()[0][x.dtype],
+                                         self.n, _ld(x, self.d), self.d, ctypes.byref(self.ptr)),
+              "pqh_flat_create_rows")
         ctx._retain()
 
     def search(self, queries, k: int, metric: str = "l2", keep=None, id_base: int = 0, out=None):
@@ -1331,18 +1349,19 @@ def flat_search_lists(ctx: Context, x_sorted, offsets, probes, queries, k: int, 
                       keep=None, id_base: int = 0, d: int = None):
     """(dist, rows), each (nq, k): for every query (device float32 (nq, >= d)) the k nearest by
     (dist, row) among the rows of the lists it probes, by the exact distances of Flat.search
-    (pqh_flat_search_lists, _ip for metric="ip").  x_sorted: device float32 (n, >= d), the rows
-    in list order; offsets: device int64 (nlist + 1,), list l at rows [offsets[l],
+    (pqh_flat_search_lists_rows, _ip for metric="ip").  x_sorted: device float32, float16 or
+    bfloat16 (n, >= d), the rows in list order (16-bit rows are searched as x_sorted.float()
+    would be, bit for bit); offsets: device int64 (nlist + 1,), list l at rows [offsets[l],
     offsets[l + 1]); probes: device int64 (nq, nprobe), -1 = none, as Coarse.probe gives them.
     rows = rows of x_sorted + id_base, padded with (+inf, -1).  keep: a device bool tensor over
     the rows of x_sorted, or the packed int32 words of pack_mask.  d: the dimensions searched
     (default: every column of x_sorted).  k <= ctx.search_max_k.  Async; ivf_status reports a
     probe outside [-1, nlist) or a bad offsets pair of a probed list (the probe skipped)."""
     torch = _torch()
-    name = "pqh_flat_search_lists" + _metric_suffix(metric, "flat_search_lists")
-    if not _rows_ok(x_sorted, 1):
-        raise PqhError(-1, "flat_search_lists: x_sorted is a device float32 tensor of shape (n, >= d) "
-                           "with unit column stride")
+    name = "pqh_flat_search_lists_rows" + _metric_suffix(metric, "flat_search_lists")
+    if not _stored_ok(x_sorted, 1):
+        raise PqhError(-1, "flat_search_lists: x_sorted is a device float32, float16 or bfloat16 "
+                           "tensor of shape (n, >= d) with unit column stride")
     n, d = x_sorted.shape[0], int(x_sorted.shape[1] if d is None else d)
     if not 1 <= d <= x_sorted.shape[1]:
         raise PqhError(-1, f"flat_search_lists: d = {d} of {x_sorted.shape[1]} columns")
@@ -1366,10 +1385,10 @@ def flat_search_lists(ctx: Context, x_sorted, offsets, probes, queries, k: int, 
         raise PqhError(-1, "flat_search_lists: keep is bool (n,) or contiguous int32 ceil(n / 32) words")
     dist = torch.empty((nq, k), dtype=torch.float32, device=probes.device)
     rows = torch.empty((nq, k), dtype=torch.int64, device=probes.device)
-    check(getattr(lib(), name)(ctx.ptr, _ptr(x_sorted) if n else None, n, _ld(x_sorted, d), d,
-                               _ptr(offsets), offsets.numel() - 1, _ptr(probes), _ptr(queries), nq,
-                               _ld(queries, d), probes.shape[1], k, _ptr(keep), id_base,
-                               _ptr(dist), _ptr(rows)), name)
+    check(getattr(lib(), name)(ctx.ptr, _ptr(x_sorted) if n else None, _row_types()[0][x_sorted.dtype],
+                               n, _ld(x_sorted, d), d, _ptr(offsets), offsets.numel() - 1,
+                               _ptr(probes), _ptr(queries), nq, _ld(queries, d), probes.shape[1], k,
+                               _ptr(keep), id_base, _ptr(dist), _ptr(rows)), name)
     return dist, rows
 
 
@@ -1395,15 +1414,37 @@ class IVFFlat:
         return self._inv
 
     @classmethod
-    def build(cls, ctx: Context, coarse: "Coarse", x, metric: str = "l2", assign: str = "direct"):
-        """the index of the rows x (device float32 (n, >= coarse.d)): coarse.assign(metric=,
-        method=assign), coarse.layout, and one gather of the rows into list order.  Async."""
+    def build(cls, ctx: Context, coarse: "Coarse", x, metric: str = "l2", assign: str = "direct",
+              store: str = None):
+        """the index of the rows x (device float32, float16 or bfloat16 (n, >= coarse.d)):
+        coarse.assign(metric=, method=assign), coarse.layout, and one gather of the rows into
+        list order.  store: the type the index keeps them in, "f32", "f16" or "bf16" (None: that
+        of x).  A 16-bit x is assigned as x.float(), in slabs of 2^20 rows at the most, so no
+        fp32 copy of all of x is made; fp32 rows stored in 16 bits are rounded once, to nearest
+        even, while they are gathered, and the lists are those of the fp32 rows.  Async."""
+        torch = _torch()
         _metric_suffix(metric, "IVFFlat.build")
-        if not _rows_ok(x, coarse.d):
-            raise PqhError(-1, "IVFFlat.build: x is a device float32 tensor of shape (n, >= d) with "
-                               "unit column stride")
-        perm, offsets = coarse.layout(coarse.assign(x, metric=metric, method=assign))
-        return cls(ctx, coarse, x[:, :coarse.d][perm].contiguous(), perm, offsets, metric)
+        types = _row_types()[1]
+        if store is not None and store not in types:
+            raise ValueError(f"IVFFlat.build: store {store!r} (None, \"f32\", \"f16\" or \"bf16\")")
+        if not _stored_ok(x, coarse.d):
+            raise PqhError(-1, "IVFFlat.build: x is a device float32, float16 or bfloat16 tensor of "
+                               "shape (n, >= d) with unit column stride")
+        if x.dtype == torch.float32:
+            list_ids = coarse.assign(x, metric=metric, method=assign)
+        else:
+            list_ids = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+            for a in range(0, x.shape[0], 1 << 20):
+                b = min(a + (1 << 20), x.shape[0])
+                coarse.assign(x[a:b].float(), out=list_ids[a:b], metric=metric, method=assign)
+        perm, offsets = coarse.layout(list_ids)
+        x_sorted = x[:, :coarse.d][perm].to(x.dtype if store is None else types[store]).contiguous()
+        return cls(ctx, coarse, x_sorted, perm, offsets, metric)
+
+    def nbytes(self) -> int:
+        """the device bytes the index owns per row, summed: the rows in list order and perm,
+        n * (d * element size + 8); the nlist + 1 offsets beside them do not grow with n"""
+        return sum(t.numel() * t.element_size() for t in (self.x_sorted, self.perm))
 
     def remove(self, ids) -> None:
         """take the rows `ids` of x (device int64, each in [0, n)) out of every later search:

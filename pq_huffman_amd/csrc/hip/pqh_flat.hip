@@ -43,7 +43,8 @@
 
 struct pqh_flat {
     pqh_ctx* ctx = nullptr;
-    const float* d_x = nullptr;   // the caller's rows, not owned
+    const void* d_x = nullptr;    // the caller's rows, not owned
+    int rows = PQH_ROWS_F32;      // their element type
     long long n = 0, ld_x = 0;
     int d = 0;
     float* d_norms = nullptr;     // [n], then Cmax
@@ -63,7 +64,7 @@ constexpr int kDiagChains = 13, kDiagFallback = 14;   // pqh_ctx::d_diag slots o
 constexpr long long kMinSlab = 1024;
 
 struct FlatArgs {
-    const float* x;
+    const void* x;       // the rows, elements of the kernel's row type T
     long long n, ld_x;
     int d, P;
     const float* norms;
@@ -85,15 +86,16 @@ __global__ void flat_clear(unsigned long long* counts, unsigned* cmax) {
     if (cmax) *cmax = 0u;
 }
 
+template <typename T>
 __global__ void __launch_bounds__(256)
-flat_norms(const float* __restrict__ x, long long n, long long ld_x, int d,
+flat_norms(const T* __restrict__ x, long long n, long long ld_x, int d,
            float* __restrict__ norms, unsigned* __restrict__ cmax) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     unsigned bits = 0u;
     if (v < n) {
         double s = 0.0;
         for (int j = 0; j < d; ++j) {
-            const double c = x[v * ld_x + j];
+            const double c = (float)x[v * ld_x + j];
             s += c * c;
         }
         const float f = (float)s;
@@ -106,13 +108,44 @@ flat_norms(const float* __restrict__ x, long long n, long long ld_x, int d,
 }
 
 // U independent chains of one lane, interleaved (a chain alone is a string of dependent
-// operations); vec: every row on 16 bytes and d % 4 == 0
-template <bool IP, int U>
-__device__ __forceinline__ void chains(const float* const (&qp)[U], const float* const (&xp)[U],
+// operations); vec: every row on 16 bytes and d % 4 == 0 (16-bit rows: d % 8 == 0, a 16-byte load
+// is eight elements, converted per step)
+template <bool IP, int U, typename T>
+__device__ __forceinline__ void chains(const float* const (&qp)[U], const T* const (&xp)[U],
                                        int d, bool vec, float (&out)[U]) {
 #pragma unroll
     for (int u = 0; u < U; ++u) out[u] = 0.f;
-    if (vec) {
+    if constexpr (kRows16<T>) {
+        if (vec) {
+#pragma unroll 1
+            for (int j = 0; j < d; j += 8) {
+                float4 a[U][2];
+                u32x4 b[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    a[u][0] = *reinterpret_cast<const float4*>(qp[u] + j);
+                    a[u][1] = *reinterpret_cast<const float4*>(qp[u] + j + 4);
+                    b[u] = *reinterpret_cast<const u32x4*>(xp[u] + j);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        chain_step<IP>(out[u], a[u][h].x, half_lo<T>(b[u][2 * h]));
+                        chain_step<IP>(out[u], a[u][h].y, half_hi<T>(b[u][2 * h]));
+                        chain_step<IP>(out[u], a[u][h].z, half_lo<T>(b[u][2 * h + 1]));
+                        chain_step<IP>(out[u], a[u][h].w, half_hi<T>(b[u][2 * h + 1]));
+                    }
+                }
+            }
+        } else {
+#pragma unroll 4
+            for (int j = 0; j < d; ++j) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) chain_step<IP>(out[u], qp[u][j], (float)xp[u][j]);
+            }
+        }
+    } else if (vec) {
 #pragma unroll 2
         for (int j = 0; j < d; j += 4) {
             float4 a[U], b[U];
@@ -140,7 +173,7 @@ __device__ __forceinline__ void chains(const float* const (&qp)[U], const float*
 
 // the all-rows path of one query over one slab: lane = row, the chain for every kept row.
 // Returns the number of chains run (wave-uniform).
-template <bool IP, int KR>
+template <bool IP, int KR, typename T>
 __device__ __forceinline__ unsigned long long all_rows(ListT<KR>& e, const float* __restrict__ qrow,
                                                        const FlatArgs& a, long long row0,
                                                        long long rows, int kth) {
@@ -157,16 +190,16 @@ __device__ __forceinline__ unsigned long long all_rows(ListT<KR>& e, const float
         const unsigned long long m = __ballot(valid);
         if (!m) continue;   // (wave-uniform)
         const float* const qp[1] = {qrow};
-        const float* const xp[1] = {a.x + (row0 + (valid ? r : base)) * a.ld_x};
+        const T* const xp[1] = {static_cast<const T*>(a.x) + (row0 + (valid ? r : base)) * a.ld_x};
         float dist[1];
-        chains<IP, 1>(qp, xp, a.d, a.vec_chain != 0, dist);
+        chains<IP, 1, T>(qp, xp, a.d, a.vec_chain != 0, dist);
         list_offer<false>(e, dist[0], r, valid, kth);
         ran += (unsigned long long)__popcll(m);
     }
     return ran;
 }
 
-template <bool IP, int KR>
+template <bool IP, int KR, typename T>
 __global__ void __launch_bounds__(64)
 flat_valu(const FlatArgs a) {
     const int lane = threadIdx.x;
@@ -176,7 +209,7 @@ flat_valu(const FlatArgs a) {
     const int k = a.k;
     ListT<KR> e;
     list_reset<KR>(e);
-    const unsigned long long ran = all_rows<IP, KR>(e, a.q + q * a.ld_q, a, row0, rows, k - 1);
+    const unsigned long long ran = all_rows<IP, KR, T>(e, a.q + q * a.ld_q, a, row0, rows, k - 1);
     const long long at = (slab * a.nq + q) * k;
     if constexpr (KR == 1) {
         if (lane < k) {
@@ -213,6 +246,23 @@ __device__ __forceinline__ void load8(const float* __restrict__ xr, int j0, int 
     }
 }
 
+// the same eight values of a row of 16-bit elements, as they lie in memory: four packed dwords
+// (zeros from d on); vec: d % 16 == 0 and every row on 16 bytes, one 16-byte load
+template <typename T>
+__device__ __forceinline__ u32x4 load8_packed(const T* __restrict__ xr, int j0, int d, bool vec) {
+    if (vec) return *reinterpret_cast<const u32x4*>(xr + j0);
+    const unsigned short* s = reinterpret_cast<const unsigned short*>(xr);
+    u32x4 v;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int e = j0 + 2 * w;
+        const unsigned lo = e < d ? (unsigned)s[min(e, d - 1)] : 0u;
+        const unsigned hi = e + 1 < d ? (unsigned)s[min(e + 1, d - 1)] : 0u;
+        v[w] = lo | hi << 16;
+    }
+    return v;
+}
+
 // LDS of flat_screen, in 4-byte words behind the two tile buffers: per wave the candidates
 // [kFlatCand][64], the drain's prefix [64] and the k-th distances [32], then the lists
 // [W][32][k] floats and [W][32][k] rows
@@ -223,9 +273,12 @@ size_t flat_lds_bytes(int P, int W, int k) {
            (size_t)W * 32 * k * 8;
 }
 
-template <bool IP, int KR, bool PAN>
+template <bool IP, int KR, bool PAN, typename XT>
 __global__ void __launch_bounds__(KR == 1 ? 256 : 64, 1)
 flat_screen(const FlatArgs a) {
+    // bf16 rows are their own high half: no low half is staged and the xl.qh pass is compiled out
+    constexpr bool kNoLow = std::is_same_v<XT, __bf16>;
+    const XT* const ax = static_cast<const XT*>(a.x);
     constexpr int W = KR == 1 ? 4 : 1, NTHR = 64 * W, PIECES = 64 * kRegPasses / NTHR;
     constexpr int TG = PAN ? kPanelTiles : 1;   // tiles whose accumulators a wave keeps
     extern __shared__ u32x4 smem[];
@@ -318,7 +371,7 @@ flat_screen(const FlatArgs a) {
         for (int p0 = 0; p0 < total; p0 += 64 * kChainU) {
             int ql[kChainU], rw[kChainU];
             const float* qp[kChainU];
-            const float* xp[kChainU];
+            const XT* xp[kChainU];
             float dist[kChainU];
 #pragma unroll
             for (int u = 0; u < kChainU; ++u) {
@@ -337,9 +390,9 @@ flat_screen(const FlatArgs a) {
                 rw[u] = cand[(pc - pre[lo]) * 64 + lo];
                 ql[u] = lo & 31;
                 qp[u] = a.q + (qw0 + ql[u]) * a.ld_q;
-                xp[u] = a.x + (row0 + rw[u]) * a.ld_x;
+                xp[u] = ax + (row0 + rw[u]) * a.ld_x;
             }
-            chains<IP, kChainU>(qp, xp, a.d, a.vec_chain != 0, dist);
+            chains<IP, kChainU, XT>(qp, xp, a.d, a.vec_chain != 0, dist);
 #pragma unroll
             for (int u = 0; u < kChainU; ++u) {
                 if (p0 + 64 * u >= total) continue;   // (wave-uniform)
@@ -367,7 +420,8 @@ flat_screen(const FlatArgs a) {
 
     // ---- the units.  Thread tid converts the pieces k * NTHR + tid of a unit: piece = (pass of
     // the panel, fragment lane), eight values of one row
-    float pre_v[PIECES][8];
+    // (16-bit rows wait as the four packed dwords they are in memory)
+    std::conditional_t<kRows16<XT>, u32x4, float[8]> pre_v[PIECES];
     float pre_n = 0.f;
     unsigned pre_m = 0u;
     auto fetch = [&](int t, int pn) {
@@ -377,11 +431,18 @@ flat_screen(const FlatArgs a) {
             const int pc = min(kk * NTHR + tid, 64 * PU - 1);   // (no branch around a load)
             const int li = pc & 63, pg = kRegPasses * pn + (pc >> 6);
             const long long row = trow + (li & 31);
-            load8(a.x + min(row, a.n - 1) * a.ld_x, 16 * min(pg, P - 1) + 8 * (li >> 5), a.d,
-                  a.vec_x != 0, pre_v[kk]);
             const bool in = row < a.n && pg < P;   // (the last panel may have fewer passes)
+            if constexpr (kRows16<XT>) {
+                pre_v[kk] = load8_packed<XT>(ax + min(row, a.n - 1) * a.ld_x,
+                                            16 * min(pg, P - 1) + 8 * (li >> 5), a.d, a.vec_x != 0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) pre_v[kk][e] = in ? pre_v[kk][e] : 0.f;
+                for (int e = 0; e < 4; ++e) pre_v[kk][e] = in ? pre_v[kk][e] : 0u;
+            } else {
+                load8(ax + min(row, a.n - 1) * a.ld_x, 16 * min(pg, P - 1) + 8 * (li >> 5), a.d,
+                      a.vec_x != 0, pre_v[kk]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) pre_v[kk][e] = in ? pre_v[kk][e] : 0.f;
+            }
         }
         // the norms start the accumulator at a tile's first panel, the word is read after its
         // last: the panels between carry neither (pn is workgroup-uniform)
@@ -405,11 +466,19 @@ flat_screen(const FlatArgs a) {
 #pragma unroll
         for (int kk = 0; kk < PIECES; ++kk) {
             const int piece = kk * NTHR + tid;
-            if (piece < 64 * PU) {
+            if constexpr (kNoLow) {
+                // h = -x: a sign flip of the packed words; there is no low half
+                if (piece < 64 * PU) dst[piece] = pre_v[kk] ^ 0x80008000u;
+            } else if (piece < 64 * PU) {
                 bf16x8 hi, lo;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float c = -pre_v[kk][e];
+                    float c;
+                    if constexpr (kRows16<XT>) {
+                        c = -(e & 1 ? half_hi<XT>(pre_v[kk][e >> 1]) : half_lo<XT>(pre_v[kk][e >> 1]));
+                    } else {
+                        c = -pre_v[kk][e];
+                    }
                     const __bf16 hb = (__bf16)c;
                     hi[e] = hb;
                     lo[e] = (__bf16)(c - (float)hb);
@@ -472,7 +541,7 @@ flat_screen(const FlatArgs a) {
                         if (kRegPasses * pn + p < P) {
                             const bf16x8 ah = __builtin_bit_cast(bf16x8, cur[p * 64 + lane]);
                             acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, Bh[p], acc[tt], 0, 0, 0);
-                            if (any_xlo) {
+                            if (!kNoLow && any_xlo) {
                                 const bf16x8 al = __builtin_bit_cast(bf16x8, cur[(PU + p) * 64 + lane]);
                                 acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, Bh[p], acc[tt], 0, 0, 0);
                             }
@@ -521,7 +590,7 @@ flat_screen(const FlatArgs a) {
         fa &= fa - 1;
         ListT<KR> e;
         list_reset<KR>(e);
-        ran += all_rows<IP, KR>(e, a.q + (qw0 + r) * a.ld_q, a, row0, rows, kth);
+        ran += all_rows<IP, KR, XT>(e, a.q + (qw0 + r) * a.ld_q, a, row0, rows, kth);
         list_to_lds<KR>(e, lds_d + r * k, lds_i + r * k, k);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -544,11 +613,11 @@ flat_screen(const FlatArgs a) {
 }
 
 // ------------------------------------------------------------------- the host side
-template <bool IP, int KR, bool PAN>
+template <bool IP, int KR, bool PAN, typename T>
 int screen_launch(pqh_ctx* ctx, const FlatArgs& a, long long groups, int slabs) {
     constexpr int W = KR == 1 ? 4 : 1;
     const size_t lds = flat_lds_bytes(a.P < kRegPasses ? a.P : kRegPasses, W, a.k);
-    const auto fn = flat_screen<IP, KR, PAN>;
+    const auto fn = flat_screen<IP, KR, PAN, T>;
     // more than 64 KB of dynamic LDS is granted once per instantiation and device: the most
     // any call can ask for (a panel of eight passes, the list's largest k).  The bitmap holds
     // devices 0 to 63; a device beyond them has no bit and is granted again on every call
@@ -566,12 +635,31 @@ int screen_launch(pqh_ctx* ctx, const FlatArgs& a, long long groups, int slabs) 
     return PQH_OK;
 }
 
-template <bool IP, int KR>
+template <bool IP, int KR, typename T>
 int valu_launch(pqh_ctx* ctx, const FlatArgs& a, int slabs) {
-    hipLaunchKernelGGL((flat_valu<IP, KR>), dim3((unsigned)a.nq, (unsigned)slabs), dim3(64), 0,
+    hipLaunchKernelGGL((flat_valu<IP, KR, T>), dim3((unsigned)a.nq, (unsigned)slabs), dim3(64), 0,
                        ctx->stream, a);
     PQH_LAUNCH_CHECK(ctx);
     return PQH_OK;
+}
+
+// the kernel of a search over rows of type T
+template <typename T>
+int flat_launch(bool ip, bool wide, bool screen, bool pan, pqh_ctx* ctx, const FlatArgs& a,
+                long long groups, int slabs) {
+    if (screen && pan)
+        return ip ? (wide ? screen_launch<true, kWideKR, true, T>(ctx, a, groups, slabs)
+                        : screen_launch<true, 1, true, T>(ctx, a, groups, slabs))
+                : (wide ? screen_launch<false, kWideKR, true, T>(ctx, a, groups, slabs)
+                        : screen_launch<false, 1, true, T>(ctx, a, groups, slabs));
+    if (screen)
+        return ip ? (wide ? screen_launch<true, kWideKR, false, T>(ctx, a, groups, slabs)
+                        : screen_launch<true, 1, false, T>(ctx, a, groups, slabs))
+                : (wide ? screen_launch<false, kWideKR, false, T>(ctx, a, groups, slabs)
+                        : screen_launch<false, 1, false, T>(ctx, a, groups, slabs));
+    return ip ? (wide ? valu_launch<true, kWideKR, T>(ctx, a, slabs) : valu_launch<true, 1, T>(ctx, a, slabs))
+                : (wide ? valu_launch<false, kWideKR, T>(ctx, a, slabs)
+                        : valu_launch<false, 1, T>(ctx, a, slabs));
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -599,11 +687,13 @@ int flat_search(bool ip, pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_
     a.q = d_queries, a.nq = nq, a.ld_q = ld_q, a.k = k, a.keep = d_keep_bits, a.id_base = id_base;
     a.kq = screen_kq(16 * a.P);
     // float4 loads where every piece lies inside a row and on 16 bytes
-    const bool x16 = flat->ld_x % 4 == 0 && aligned16(flat->d_x);
+    // (16 bytes are eight elements of a 16-bit row)
+    const int per16 = flat->rows == PQH_ROWS_F32 ? 4 : 8;
+    const bool x16 = flat->ld_x % per16 == 0 && aligned16(flat->d_x);
     const bool q16 = ld_q % 4 == 0 && aligned16(d_queries);
     a.vec_x = d % 16 == 0 && x16;
     a.vec_q = d % 16 == 0 && q16;
-    a.vec_chain = d % 4 == 0 && x16 && q16;
+    a.vec_chain = d % per16 == 0 && x16 && q16;
 
     // the slabs: about one workgroup per compute unit (the screen's LDS admits one), a wave's
     // worth of them for the VALU kernel; multiples of 32 rows, kMinSlab at least, so that the
@@ -630,20 +720,9 @@ int flat_search(bool ip, pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_
         PQH_LAUNCH_CHECK(ctx);
         a.counts = ctx->d_diag;
     }
-    if (screen && pan)
-        rc = ip ? (wide ? screen_launch<true, kWideKR, true>(ctx, a, groups, slabs)
-                        : screen_launch<true, 1, true>(ctx, a, groups, slabs))
-                : (wide ? screen_launch<false, kWideKR, true>(ctx, a, groups, slabs)
-                        : screen_launch<false, 1, true>(ctx, a, groups, slabs));
-    else if (screen)
-        rc = ip ? (wide ? screen_launch<true, kWideKR, false>(ctx, a, groups, slabs)
-                        : screen_launch<true, 1, false>(ctx, a, groups, slabs))
-                : (wide ? screen_launch<false, kWideKR, false>(ctx, a, groups, slabs)
-                        : screen_launch<false, 1, false>(ctx, a, groups, slabs));
-    else
-        rc = ip ? (wide ? valu_launch<true, kWideKR>(ctx, a, slabs) : valu_launch<true, 1>(ctx, a, slabs))
-                : (wide ? valu_launch<false, kWideKR>(ctx, a, slabs)
-                        : valu_launch<false, 1>(ctx, a, slabs));
+    rc = flat->rows == PQH_ROWS_F16    ? flat_launch<_Float16>(ip, wide, screen, pan, ctx, a, groups, slabs)
+         : flat->rows == PQH_ROWS_BF16 ? flat_launch<__bf16>(ip, wide, screen, pan, ctx, a, groups, slabs)
+                                       : flat_launch<float>(ip, wide, screen, pan, ctx, a, groups, slabs);
     if (rc || slabs == 1) return rc;
     return pqh_topk_merge(ctx, a.out_d, a.out_id, slabs, nq, k, nullptr, k, d_dist, d_ids);
 }
@@ -652,8 +731,9 @@ int flat_search(bool ip, pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_
 
 extern "C" {
 
-int pqh_flat_create(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
-                    pqh_flat_t** flat) {
+int pqh_flat_create_rows(pqh_ctx_t* ctx, const void* d_x, int rows, long long n, long long ld_x,
+                         int d, pqh_flat_t** flat) {
+    if (!pqh_rows_ok(rows, d_x)) return PQH_ERR_ARG;
     if (!ctx) return pqh_no_ctx_status();
     if (!flat || n < 0 || d < 1 || ld_x < d || (n > 0 && !d_x)) return PQH_ERR_ARG;
     if (n > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
@@ -661,7 +741,7 @@ int pqh_flat_create(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_
     if (rc) return rc;
     pqh_flat* f = new (std::nothrow) pqh_flat;
     if (!f) return PQH_ERR_NOMEM;
-    f->ctx = ctx, f->d_x = d_x, f->n = n, f->ld_x = ld_x, f->d = d;
+    f->ctx = ctx, f->d_x = d_x, f->rows = rows, f->n = n, f->ld_x = ld_x, f->d = d;
     const size_t bytes = ((size_t)n + 1) * 4;
     if (hipMalloc(&f->d_norms, bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -671,9 +751,16 @@ int pqh_flat_create(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_
     f->d_cmax = reinterpret_cast<unsigned*>(f->d_norms + n);
     hipLaunchKernelGGL(flat_clear, dim3(1), dim3(1), 0, ctx->stream,
                        (unsigned long long*)nullptr, f->d_cmax);
-    if (n > 0)
-        hipLaunchKernelGGL(flat_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           d_x, n, ld_x, d, f->d_norms, f->d_cmax);
+    const dim3 nb((unsigned)((n + 255) / 256));
+    if (n > 0 && rows == PQH_ROWS_F32)
+        hipLaunchKernelGGL(flat_norms<float>, nb, dim3(256), 0, ctx->stream,
+                           static_cast<const float*>(d_x), n, ld_x, d, f->d_norms, f->d_cmax);
+    else if (n > 0 && rows == PQH_ROWS_F16)
+        hipLaunchKernelGGL(flat_norms<_Float16>, nb, dim3(256), 0, ctx->stream,
+                           static_cast<const _Float16*>(d_x), n, ld_x, d, f->d_norms, f->d_cmax);
+    else if (n > 0)
+        hipLaunchKernelGGL(flat_norms<__bf16>, nb, dim3(256), 0, ctx->stream,
+                           static_cast<const __bf16*>(d_x), n, ld_x, d, f->d_norms, f->d_cmax);
     if (hipGetLastError() != hipSuccess) {
         (void)hipFree(f->d_norms);
         delete f;
@@ -681,6 +768,11 @@ int pqh_flat_create(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_
     }
     *flat = f;
     return PQH_OK;
+}
+
+int pqh_flat_create(pqh_ctx_t* ctx, const float* d_x, long long n, long long ld_x, int d,
+                    pqh_flat_t** flat) {
+    return pqh_flat_create_rows(ctx, d_x, PQH_ROWS_F32, n, ld_x, d, flat);
 }
 
 int pqh_flat_destroy(pqh_flat_t* flat) {

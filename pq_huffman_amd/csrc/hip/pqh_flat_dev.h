@@ -24,6 +24,31 @@ __device__ __forceinline__ void chain_step(float& acc, float qv, float xv) {
     }
 }
 
+// ------------------------------------------------------------------- rows of 16-bit values
+// A row type is the compiler's own element type: float, _Float16 (PQH_ROWS_F16) or __bf16
+// (PQH_ROWS_BF16).  Every 16-bit value is an fp32 value, so (float) of an element is exact; the
+// fp16 conversion is the hardware's (v_cvt_f32_f16, subnormals kept), the bf16 one a shift.
+template <typename T>
+constexpr bool kRows16 = !std::is_same_v<T, float>;
+
+// the low and the high half of a dword of a row, as fp32
+template <typename T>
+__device__ __forceinline__ float half_lo(unsigned w) {
+    if constexpr (std::is_same_v<T, __bf16>) {
+        return __uint_as_float(w << 16);
+    } else {
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu));
+    }
+}
+template <typename T>
+__device__ __forceinline__ float half_hi(unsigned w) {
+    if constexpr (std::is_same_v<T, __bf16>) {
+        return __uint_as_float(w & 0xFFFF0000u);
+    } else {
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
+    }
+}
+
 // ------------------------------------------------------------------- the groups of a list scan
 // (host) The groups a unit of the list scans is cut into (flat_lists, sq_lists).  The lists'
 // lengths are device data, so the plan goes by the mean list: a group per kSegRows rows of it;

@@ -76,6 +76,11 @@ int pqh_use_device(pqh_ctx* ctx);
 // what a call answers to a NULL context -- all a process without a GPU can have, since
 // pqh_ctx_create fails there: PQH_ERR_NO_DEVICE when no HIP device is visible, else PQH_ERR_ARG
 int pqh_no_ctx_status();
+// a row type of the *_rows calls (PQH_ROWS_*) that is known, and rows that lie on its element size
+inline bool pqh_rows_ok(int rows, const void* d_x) {
+    if (rows != PQH_ROWS_F32 && rows != PQH_ROWS_F16 && rows != PQH_ROWS_BF16) return false;
+    return (reinterpret_cast<uintptr_t>(d_x) & (rows == PQH_ROWS_F32 ? 3u : 1u)) == 0;
+}
 int pqh_kmeans_fixed_shift(float max_abs, long long n);
 // k-means iteration pieces (pqh_kmeans.hip), shared by the one-shot and the streamed trainers
 int pqh_kmeans_absmax_launch(pqh_ctx* ctx, const float* d_x, long long n, long long ld_x, int d,
