@@ -1412,6 +1412,58 @@ int pqh_sq_search_lists_ip(pqh_ctx_t* ctx, const unsigned char* d_codes, long lo
                            int top_k, const unsigned int* d_keep_bits, long long id_base,
                            float* d_dist, long long* d_ids);
 
+/* ---- exact re-rank: a search's candidates scored against stored rows --------------------------
+ * The second stage of an inverted file: a cheap scan names ncand candidates a query, these calls
+ * score them against a row store indexed by the candidates' ids and return the best top_k.
+ * The definition.  For query q and candidate id r, 0 <= r < n:
+ *   acc = +0;  for j = 0 .. d - 1:  L2  t = q[j] - row_r[j], acc = acc + t * t;
+ *                                   inner product  acc = acc - q[j] * row_r[j];   dist = acc
+ * fp32 throughout, j ascending, one chain, every operation rounded once, no fused multiply-add:
+ * the bits pqh_flat_search and pqh_flat_search_lists return for that pair.  row_r[j] is the
+ * stored value: an fp32 value itself, a 16-bit value converted exactly (pqh_rerank_rows: rows of
+ * the type `rows`, PQH_ROWS_*, ld_x >= d ELEMENTS apart, d_x on the element's size), an SQ8 code
+ * decoded as dec = fl(vmin[j] + fl((float)code * step[j])) (pqh_rerank_sq: d_codes, ld_c >= d
+ * bytes apart, and the quantizer's two arrays, as in pqh_sq_decode).
+ * For each query q < nq (rows of d_queries ld_q >= d floats apart): of the candidates
+ * d_cand[q][0 .. ncand) (int64 ids, contiguous) the top_k smallest by (dist, id) ascending, padded
+ * with (+inf, -1), into d_dist[q][0 .. top_k) and d_ids[q][0 .. top_k); the rows of both outputs
+ * are ld_out >= top_k elements apart and what lies between them is left alone.  A candidate -1 is
+ * padding and is skipped; an id below -1 or >= n is dropped and makes pqh_ivf_status answer
+ * PQH_ERR_ARG (as a bad row of pqh_sq_decode does); an id named twice is scored twice and may be
+ * returned twice.  So the outcome is the flat search's order over the candidate subset.  A
+ * candidate whose distance is +inf or NaN is not told from padding, as in pqh_refine_*.
+ * 1 <= top_k <= ncand <= the context's limit (PQH_SEARCH_MAX_K, or what
+ * pqh_ctx_set_search_max_k set, 256 at the most); any d >= 1.  The elements from d to ld of a
+ * row are never used, and nothing outside the n * ld elements of the store is read.  There is no
+ * mask and no id_base: the candidates are already filtered, and they are ids of the store.
+ * Conventions: device pointers, asynchronous on the context's stream, no scratch.  The order of
+ * the checks is pqh_sq_search_lists': (pqh_rerank_rows: an unknown `rows` or a d_x off its
+ * element size is PQH_ERR_ARG, answered first;) PQH_ERR_ARG for n < 0, d < 1, ld_x (ld_c) < d,
+ * nq < 0, ld_q < d, ncand < 1 or > 256, top_k < 1 or > ncand, ld_out < top_k, and with nq > 0 a
+ * null d_queries, d_cand, d_dist or d_ids or (n > 0) a null store, d_vmin or d_step; then a NULL
+ * context is answered as in the search calls; then ncand above the context's limit is
+ * PQH_ERR_ARG; then PQH_ERR_UNSUPPORTED for nq >= 2^31 or n * ld >= 2^63.  nq == 0 is a success
+ * that launches nothing; n == 0 gives all padding and reports every candidate but -1.
+ * Fast path: a row's 128 bytes are read 16 bytes a lane where the rows' distance in bytes is a
+ * multiple of 4 and the store lies on 4 bytes (fp32 rows always; an even ld_x of 16-bit rows;
+ * ld_c % 4 == 0); else element by element. */
+int pqh_rerank_rows(pqh_ctx_t* ctx, const void* d_x, int rows /* PQH_ROWS_* */, long long n,
+                    long long ld_x, int d, const float* d_queries, long long nq, long long ld_q,
+                    const long long* d_cand /* [nq][ncand] */, int ncand, int top_k,
+                    float* d_dist, long long* d_ids, long long ld_out);
+int pqh_rerank_rows_ip(pqh_ctx_t* ctx, const void* d_x, int rows, long long n, long long ld_x,
+                       int d, const float* d_queries, long long nq, long long ld_q,
+                       const long long* d_cand, int ncand, int top_k, float* d_dist,
+                       long long* d_ids, long long ld_out);
+int pqh_rerank_sq(pqh_ctx_t* ctx, const unsigned char* d_codes, long long n, long long ld_c, int d,
+                  const float* d_vmin, const float* d_step, const float* d_queries, long long nq,
+                  long long ld_q, const long long* d_cand /* [nq][ncand] */, int ncand, int top_k,
+                  float* d_dist, long long* d_ids, long long ld_out);
+int pqh_rerank_sq_ip(pqh_ctx_t* ctx, const unsigned char* d_codes, long long n, long long ld_c,
+                     int d, const float* d_vmin, const float* d_step, const float* d_queries,
+                     long long nq, long long ld_q, const long long* d_cand, int ncand, int top_k,
+                     float* d_dist, long long* d_ids, long long ld_out);
+
 /* Host: (this rank's global bit offset, the global length) from every rank's bit length. */
 int pqh_shard_offsets(const unsigned long long* lengths, int world, int rank,
                       unsigned long long* offset, unsigned long long* total);

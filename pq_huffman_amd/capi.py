@@ -267,6 +267,12 @@ SIGNATURES = [
     ("pqh_sq_decode", I, [P, P, LL, LL, I, P, P, P, LL, LL, P, LL]),
     ("pqh_sq_search_lists", I, [P, P, LL, LL, I, P, P, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
     ("pqh_sq_search_lists_ip", I, [P, P, LL, LL, I, P, P, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),
+    # the exact re-rank.  rows: x, rows' type, n, ld_x, d; sq: codes, n, ld_c, d, vmin, step; then
+    # queries, nq, ld_q, cand, ncand, top_k, dist, ids, ld_out
+    ("pqh_rerank_rows", I, [P, P, I, LL, LL, I, P, LL, LL, P, I, I, P, P, LL]),
+    ("pqh_rerank_rows_ip", I, [P, P, I, LL, LL, I, P, LL, LL, P, I, I, P, P, LL]),
+    ("pqh_rerank_sq", I, [P, P, LL, LL, I, P, P, P, LL, LL, P, I, I, P, P, LL]),
+    ("pqh_rerank_sq_ip", I, [P, P, LL, LL, I, P, P, P, LL, LL, P, I, I, P, P, LL]),
     ("pqh_shard_offsets", I, [P, I, I, P, P]),
     ("pqh_shard_stitch", I, [I, P, P, P, P, ULL]),
     ("pqh_shard_halo_source", I, [P, I, I, P, P]),

@@ -1630,6 +1630,68 @@ class IVFSQ(IVFFlat):
                    for t in (self.codes, self.perm, self.offsets, self.sq.vmin, self.sq.step))
 
 
+def _store_parts(store, d, what: str):
+    """(sq or None, the tensor of rows, d) of a re-rank store: a device float32, float16 or
+    bfloat16 tensor (n, >= d), or a pair (SQ, uint8 codes (n, >= sq.d)); d None: every column of
+    the tensor, sq.d of a pair"""
+    if isinstance(store, (tuple, list)):
+        if len(store) != 2 or not isinstance(store[0], SQ) or not store[0]._codes_ok(store[1]) or \
+                (d is not None and int(d) != store[0].d):
+            raise PqhError(-1, f"{what}: a store of codes is a pair (SQ, device uint8 tensor of shape "
+                               "(n, >= sq.d) with unit column stride), and d is sq.d")
+        return store[0], store[1], store[0].d
+    if not hasattr(store, "dtype") or not _stored_ok(store, 1):
+        raise PqhError(-1, f"{what}: store is a device float32, float16 or bfloat16 tensor of shape "
+                           "(n, >= d) with unit column stride, or a pair (SQ, codes)")
+    d = int(store.shape[1] if d is None else d)
+    if not 1 <= d <= store.shape[1]:
+        raise PqhError(-1, f"{what}: d = {d} of {store.shape[1]} columns")
+    return None, store, d
+
+
+def rerank(ctx: Context, store, queries, cand, k: int, metric: str = "l2", d: int = None, out=None):
+    """(dist, ids), each (nq, k): the candidates cand[q] (device int64 (nq, ncand), ids = rows of
+    the store, -1 = padding, ncand <= ctx.search_max_k) of every query (device float32
+    (nq, >= d)) re-ranked by the exact distance of Flat.search to their stored rows; the
+    k <= ncand smallest by (dist, id), padded with (+inf, -1) (pqh_rerank_rows, pqh_rerank_sq,
+    _ip for metric="ip").  store: a device float32, float16 or bfloat16 tensor (n, >= d) with
+    unit column stride (16-bit rows are scored as store.float() would be, bit for bit), or a pair
+    (sq, codes) of a codec.SQ and its uint8 codes, scored as sq.decode(codes) would be.  d: the
+    dimensions scored (default: every column of the tensor; sq.d for codes).  An id named twice
+    is scored twice.  out: a (dist, ids) pair to fill, rows out[0].stride(0) apart in both.
+    Async; ivf_status reports an id below -1 or >= n (dropped)."""
+    torch = _torch()
+    sfx = _metric_suffix(metric, "rerank")
+    sq, x, d = _store_parts(store, d, "rerank")
+    n = x.shape[0]
+    if not _rows_ok(queries, d) or (queries.numel() and x.numel() and queries.device != x.device):
+        raise PqhError(-1, "rerank: queries is a float32 tensor of shape (nq, >= d) with unit column "
+                           "stride on the device of the store")
+    nq = queries.shape[0]
+    if cand.dtype != torch.int64 or cand.dim() != 2 or not cand.is_contiguous() or \
+            cand.shape[0] != nq or (cand.numel() and not cand.is_cuda):
+        raise PqhError(-1, "rerank: cand is a contiguous device int64 tensor of shape (nq, ncand)")
+    ncand = cand.shape[1]
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=cand.device),
+               torch.empty((nq, k), dtype=torch.int64, device=cand.device))
+    dist, ids = out
+    ld = dist.stride(0) if nq > 1 else max(k, 1)
+    if nq > 1 and ids.stride(0) != ld or (k > 1 and (dist.stride(1) != 1 or ids.stride(1) != 1)):
+        raise PqhError(-1, "rerank: out is a pair of tensors with rows the same distance apart")
+    tail = (_ptr(queries), nq, _ld(queries, d), _ptr(cand), ncand, k, _ptr(dist), _ptr(ids), ld)
+    if sq is None:
+        name = "pqh_rerank_rows" + sfx
+        rc = getattr(lib(), name)(ctx.ptr, _ptr(x) if n else None, _row_types()[0][x.dtype], n,
+                                  _ld(x, d), d, *tail)
+    else:
+        name = "pqh_rerank_sq" + sfx
+        rc = getattr(lib(), name)(ctx.ptr, _ptr(x) if n else None, n, _ld(x, d), d, _ptr(sq.vmin),
+                                  _ptr(sq.step), *tail)
+    check(rc, name)
+    return dist, ids
+
+
 class Rotation:
     """A d x d matrix on the device (pqh_rotation_t), applied to rows before the quantizers see
     them: the learned rotation of OPQ.  R: host float32 (d, d), 1 <= d <= 1024.  Any matrix is
@@ -2027,6 +2089,7 @@ class IVF:
         self.assign_method = "direct"   # build(assign=...): Coarse.assign's method, add() keeps it
         self.refine_pq = self.refine_tables = self.refine_enc = None   # build(refine_pq=...)
         self.rotation = None     # build(rotation=...): the index lives in the rotated space
+        self.rows = None         # set_rows(): the caller's row store of search(rerank=...)
         self.live = None         # remove(): device bool per stream row, allocated on first use
         self._live_words = None  # its packed form, made again after a remove()
 
@@ -2135,6 +2198,16 @@ class IVF:
     def _perm(self):
         """perm, decoded for the length of a call where the index holds an IdMap"""
         return self.perm if self.idmap is None else self.idmap.decode()
+
+    def set_rows(self, store) -> None:
+        """attach the row store of search(rerank=...): what codec.rerank takes as `store`, a
+        device float32, float16 or bfloat16 tensor (>= n_ids, >= d) or a pair (sq, codes), row i
+        the row of id i in the caller's own axes (in front of any rotation=).  It stays the
+        caller's: nothing is copied, and after add() the caller attaches the grown store.  None
+        detaches it."""
+        if store is not None:
+            _store_parts(store, self.coarse.d, "IVF.set_rows")
+        self.rows = store
 
     def remove(self, ids) -> None:
         """take the caller rows `ids` (device int64, each in [0, n)) out of every later search,
@@ -2284,7 +2357,7 @@ class IVF:
         return words if self._live_words is None else words & self._live_words
 
     def search(self, queries, nprobe: int, k: int, schedule: str = "query", keep=None,
-               refine: int = 0):
+               refine: int = 0, rerank: int = 0):
         """(dist, ids), each (nq, k): the k nearest rows by ADC distance among the rows of each
         query's nprobe nearest lists; ids are rows of the caller's x, padded with (+inf, -1).
         schedule: "query" decodes a list once for every query that probes it (search_ranges),
@@ -2297,10 +2370,28 @@ class IVF:
         with
         refine_pq: the scan returns its c best rows and the k best of those by the refined
         distance (both levels' reconstructions added, codec.refine) are the result, their
-        distances the refined ones."""
+        distances the refined ones.
+        rerank: 0, or the number c of candidates, k <= c <= ctx.search_max_k, on an index with a
+        row store (set_rows): the scan returns its c best rows, and the k best of those by the
+        exact distance to their stored rows (codec.rerank, the index's metric, the caller's own
+        queries in front of any rotation) are the result, ordered by (exact dist, id).  Not
+        together with refine."""
         torch = _torch()
         if schedule not in ("query", "list", "auto"):
             raise PqhError(-1, f"IVF.search: schedule {schedule!r}")
+        if rerank:
+            if refine:
+                raise PqhError(-1, "IVF.search: rerank and refine are two second stages; give one")
+            if self.rows is None:
+                raise PqhError(-1, "IVF.search: rerank > 0 on an index without a row store (set_rows)")
+            have = _store_parts(self.rows, self.coarse.d, "IVF.search")[1].shape[0]
+            if have < self.n_ids:
+                raise PqhError(-1, f"IVF.search: the row store has {have} rows for {self.n_ids} ids "
+                                   "(after add(), attach the grown store)")
+            limit = self.ctx.search_max_k
+            if not k <= rerank <= limit:
+                raise PqhError(-1, f"IVF.search: rerank = {rerank} outside [k, {limit}]")
+            exact_k, k, own = k, rerank, queries
         if refine:
             if self.refine_pq is None:
                 raise PqhError(-1, "IVF.search: refine > 0 on an index built without refine_pq")
@@ -2317,6 +2408,8 @@ class IVF:
         if self.residual:
             dist, rows = self._search_residual(queries, nprobe, k, by_list, mask,
                                                top_k if refine else 0)
+            if rerank:
+                return self._rerank(own, rows, exact_k)
             return dist, self._ids_of(rows)
         lut = adc_tables(self.ctx, self.pq, queries, metric=self.metric)
         range_ptr, ranges, probes, _ = self.coarse.probe(queries, nprobe, self.offsets,
@@ -2329,7 +2422,14 @@ class IVF:
                                        keep=mask)
         if refine:
             dist, rows = self._refine(queries, rows, top_k)
+        if rerank:
+            return self._rerank(own, rows, exact_k)
         return dist, self._ids_of(rows)
+
+    def _rerank(self, queries, rows, k: int):
+        """(exact dist, ids): the k best of the scan's candidate rows by their stored rows"""
+        return rerank(self.ctx, self.rows, queries, self._ids_of(rows).contiguous(), k,
+                      metric=self.metric, d=self.coarse.d)
 
     def _refine(self, queries, rows, k: int, out=None):
         """(dist, stream rows): the k best of the scan's candidate rows by both levels' codes"""
