@@ -1266,6 +1266,60 @@ int pqh_flat_search_ip(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_qu
  * query when d > 1,024). */
 int pqh_flat_last_counts(pqh_ctx_t* ctx, unsigned long long* chains, unsigned long long* fallback);
 
+/* Range search over the rows of a pqh_flat_t, fp32, fp16 or bf16: row v is a hit of query q iff
+ * it is kept (d_keep_bits as above), v < n and dist(q, v) < d_radius[q], strictly; dist is
+ * pqh_flat_search's chain bit for bit (the _ip calls: the negated inner product, so dist < radius
+ * is ip > -radius).  A NaN radius or a NaN distance is no hit; an L2 radius <= 0 has none.  The
+ * result is the CSR form of pqh_range_count_* / pqh_range_fill_*: d_lims [nq + 1] (int64,
+ * d_lims[0] = 0), query q's hits entries [d_lims[q], d_lims[q + 1]) of d_dist / d_ids in
+ * ascending row, ids = id_base + v.  Bits and order depend neither on the grid nor on the tuning.
+ * The chain is run only for the pairs the matrix-instruction screen of pqh_flat_search cannot
+ * rule out against the radius (d <= 1,024; above it, and for a query with a non-finite value or
+ * beside a non-finite row, for every kept row), by a bound that is proven.
+ * Two passes over a plan in the CALLER's device memory (8-byte aligned, at least
+ * pqh_flat_range_plan_bytes bytes: a header, 8 bytes per query and slab of rows, 16 more):
+ *   pqh_flat_range_count / _ip  screens, counts every query's hits per slab into the plan, turns
+ *                      the counts into offsets and writes d_lims.  The header records the geometry
+ *                      (n, nq, d, the slabs and query groups).
+ *   pqh_flat_range_fill / _ip   takes the same arguments, the plan and d_lims as the count left
+ *                      them, and screens again: every hit is written at its offset.  Entry p is
+ *                      written only if p < capacity, so a buffer that is too small holds the first
+ *                      `capacity` entries of the full result and nothing past it is touched;
+ *                      d_lims always holds the full counts, and truncation is no error.  A
+ *                      workgroup whose queries counted nothing in its slab reads no row.  The fill
+ *                      may be repeated.
+ * Nothing on the context has to survive between the two calls.  A fill whose own geometry is not
+ * the plan's (PQH_TUNE_SEARCH_GROUPS, which sets the slabs outright, changed in between; another
+ * object or nq) writes nothing and sets the sticky bit that pqh_decode_status reports as
+ * PQH_ERR_ARG.  Async.  Checks and limits are pqh_flat_search's: ctx is the context the object
+ * was made with, nq < 2^31 (more: PQH_ERR_UNSUPPORTED), 0 <= id_base <= 2^63 - 1 - n, a 4-byte
+ * aligned mask, ld_q >= d, capacity >= 0, plan_bytes at least pqh_flat_range_plan_bytes, no null
+ * pointer with nq > 0 (d_dist / d_ids may be NULL when capacity == 0), else PQH_ERR_ARG.  nq == 0
+ * launches nothing, n == 0 only the write of d_lims (all zero).  pqh_flat_last_counts reports a
+ * count or a fill as it reports a search. */
+int pqh_flat_range_plan_bytes(pqh_ctx_t* ctx, const pqh_flat_t* flat, long long nq,
+                              unsigned long long* bytes);
+int pqh_flat_range_count(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_queries,
+                         long long nq, long long ld_q, const float* d_radius /* [nq] */,
+                         const unsigned int* d_keep_bits /* or NULL */, void* d_plan,
+                         unsigned long long plan_bytes, long long* d_lims /* [nq + 1] */);
+int pqh_flat_range_count_ip(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_queries,
+                            long long nq, long long ld_q, const float* d_radius,
+                            const unsigned int* d_keep_bits, void* d_plan,
+                            unsigned long long plan_bytes, long long* d_lims);
+int pqh_flat_range_fill(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_queries,
+                        long long nq, long long ld_q, const float* d_radius,
+                        const unsigned int* d_keep_bits, const void* d_plan,
+                        unsigned long long plan_bytes, const long long* d_lims,
+                        long long capacity, long long id_base, float* d_dist /* [capacity] */,
+                        long long* d_ids /* [capacity] */);
+int pqh_flat_range_fill_ip(pqh_ctx_t* ctx, const pqh_flat_t* flat, const float* d_queries,
+                           long long nq, long long ld_q, const float* d_radius,
+                           const unsigned int* d_keep_bits, const void* d_plan,
+                           unsigned long long plan_bytes, const long long* d_lims,
+                           long long capacity, long long id_base, float* d_dist,
+                           long long* d_ids);
+
 /* ---- IVF-Flat: the exact top-k over the raw rows of probed lists ---------------------------
  * pqh_flat_search's distances and order, restricted per query to the rows of the lists it
  * probes: d_x are the rows IN LIST ORDER (ld_x >= d floats apart, the floats between rows never

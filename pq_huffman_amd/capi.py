@@ -251,6 +251,13 @@ SIGNATURES = [
     ("pqh_flat_search", I, [P, P, P, LL, LL, I, P, LL, P, P]),
     ("pqh_flat_search_ip", I, [P, P, P, LL, LL, I, P, LL, P, P]),
     ("pqh_flat_last_counts", I, [P, P, P]),
+    # the flat range search: flat, queries, nq, ld_q, radius, keep, plan, plan_bytes, lims; the
+    # fills then capacity, id_base, dist, ids
+    ("pqh_flat_range_plan_bytes", I, [P, P, LL, P]),
+    ("pqh_flat_range_count", I, [P, P, P, LL, LL, P, P, P, ULL, P]),
+    ("pqh_flat_range_count_ip", I, [P, P, P, LL, LL, P, P, P, ULL, P]),
+    ("pqh_flat_range_fill", I, [P, P, P, LL, LL, P, P, P, ULL, P, LL, LL, P, P]),
+    ("pqh_flat_range_fill_ip", I, [P, P, P, LL, LL, P, P, P, ULL, P, LL, LL, P, P]),
     # IVF-Flat: x, n, ld_x, d, offsets, nlist, probes, queries, nq, ld_q, nprobe, top_k, keep,
     # id_base, dist, ids
     ("pqh_flat_search_lists", I, [P, P, LL, LL, I, P, LL, P, P, LL, LL, I, I, P, LL, P, P]),

@@ -1303,19 +1303,72 @@ class Flat:
                 all(t.shape == (nq, k) and t.is_contiguous() and t.device == self.x.device
                     for t in out)):
             raise PqhError(-1, "Flat.search: out is a contiguous (float32, int64) pair of shape (nq, k) on the device of x")
-        if keep is not None and keep.dtype in (torch.bool, torch.uint8):
-            if keep.numel() != self.n:
-                raise PqhError(-1, f"Flat.search: {keep.numel()} keep flags for {self.n} rows")
-            keep = pack_mask(self.ctx, keep)
-        if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
-                                 keep.numel() < (self.n + 31) // 32):
-            raise PqhError(-1, "Flat.search: keep is bool (n,) or contiguous int32 ceil(n / 32) words")
+        keep = self._keep_words(keep, "Flat.search")
         if out is None:
             out = (torch.empty((nq, k), dtype=torch.float32, device=queries.device),
                    torch.empty((nq, k), dtype=torch.int64, device=queries.device))
         check(getattr(lib(), name)(self.ctx.ptr, self.ptr, _ptr(queries), nq, _ld(queries, self.d),
                                    k, _ptr(keep), id_base, _ptr(out[0]), _ptr(out[1])), name)
         return out
+
+    def _keep_words(self, keep, what: str):
+        """keep as the calls take it: None, or the packed int32 words of a row mask"""
+        torch = _torch()
+        if keep is not None and keep.dtype in (torch.bool, torch.uint8):
+            if keep.numel() != self.n:
+                raise PqhError(-1, f"{what}: {keep.numel()} keep flags for {self.n} rows")
+            keep = pack_mask(self.ctx, keep)
+        if keep is not None and (keep.dtype != torch.int32 or not keep.is_contiguous() or
+                                 keep.numel() < (self.n + 31) // 32):
+            raise PqhError(-1, f"{what}: keep is bool (n,) or contiguous int32 ceil(n / 32) words")
+        return keep
+
+    def range_search(self, queries, radius, metric: str = "l2", keep=None, id_base: int = 0,
+                     capacity=None):
+        """(lims, dist, ids): every kept row with dist < radius[q] (strict; search()'s distance,
+        bit for bit), as many as there are, in CSR form: query q's hits are dist / ids
+        [lims[q], lims[q + 1]) in ascending row, ids = rows + id_base; lims int64 (nq + 1,), dist
+        float32 and ids int64 (lims[nq],).  metric="ip": dist is the negated inner product, so
+        dist < radius is ip > -radius.  A NaN radius or distance is no hit.  Two passes of the
+        screen (pqh_flat_range_count, pqh_flat_range_fill): the first counts, the second writes.
+        radius: a float, or a device float32 tensor (nq,).  keep: what search() takes.
+        capacity=None: the outputs are allocated exactly, which waits once for the device to read
+        lims[-1] between the passes.  capacity=int: no wait; dist and ids have that length, hold
+        the first `capacity` entries of the result and (+inf, -1) behind lims[-1]; lims always
+        holds the full counts.  Async otherwise; counts() reports the fill."""
+        torch = _torch()
+        suffix = _metric_suffix(metric, "Flat.range_search")
+        if not _rows_ok(queries, self.d) or (queries.numel() and self.x.numel() and
+                                             queries.device != self.x.device):
+            raise PqhError(-1, "Flat.range_search: queries is a float32 tensor of shape (nq, >= d) "
+                               "with unit column stride on the device of x")
+        nq, dev = queries.shape[0], self.x.device if self.x.numel() else queries.device
+        if torch.is_tensor(radius):
+            if radius.dtype != torch.float32 or radius.shape != (nq,):
+                raise PqhError(-1, f"Flat.range_search: radius is a float or a float32 tensor of shape ({nq},)")
+            radius = radius.contiguous()
+        else:
+            radius = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+        keep = self._keep_words(keep, "Flat.range_search")
+        nbytes = ctypes.c_ulonglong(0)
+        check(lib().pqh_flat_range_plan_bytes(self.ctx.ptr, self.ptr, nq, ctypes.byref(nbytes)),
+              "pqh_flat_range_plan_bytes")
+        plan = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=dev)
+        lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)   # (nq == 0 launches nothing)
+        args = (self.ctx.ptr, self.ptr, _ptr(queries), nq, _ld(queries, self.d), _ptr(radius),
+                _ptr(keep), _ptr(plan), plan.numel() * 8, _ptr(lims))
+        check(getattr(lib(), "pqh_flat_range_count" + suffix)(*args), "pqh_flat_range_count" + suffix)
+        if capacity is None:
+            capacity = int(lims[-1].item())     # the one synchronisation
+            dist = torch.empty(capacity, dtype=torch.float32, device=dev)
+            ids = torch.empty(capacity, dtype=torch.int64, device=dev)
+        else:
+            dist = torch.full((capacity,), float("inf"), dtype=torch.float32, device=dev)
+            ids = torch.full((capacity,), -1, dtype=torch.int64, device=dev)
+        check(getattr(lib(), "pqh_flat_range_fill" + suffix)(*args, capacity, id_base, _ptr(dist),
+                                                             _ptr(ids)),
+              "pqh_flat_range_fill" + suffix)
+        return lims, dist, ids
 
     def counts(self):
         """(chains, fallback) of the context's last flat search that had work: the (query, row)

@@ -147,6 +147,12 @@ int pqh_list_plan_launch(pqh_ctx* ctx, pqh_list_plan* p);
 int pqh_lists_merge_launch(pqh_ctx* ctx, const float* part_d, const long long* part_id,
                            long long lists, long long nq, int top_k, long long id_base,
                            float* d_dist, long long* d_ids);
+// the range searches' plan (pqh_radius.hip), for the range search of another file
+// (pqh_flat_range.hip): radius_offsets over ent [nq * shares + 1], counts ordered (query, share),
+// into exclusive prefixes and lims [nq + 1]; and the lims of a call without rows, all zero
+int pqh_range_offsets_launch(pqh_ctx* ctx, long long* ent, long long shares, long long nq,
+                             long long* lims);
+int pqh_range_no_rows_launch(pqh_ctx* ctx, long long nq, long long* lims);
 // pqh_shard_encode's histogram / size / write with this shard's raw-first flag in device
 // memory (1: row 0 raw, no halo pair; 0: row 0 in the context of d_prev_row) -- pqh_huff.hip
 extern "C" {

@@ -415,12 +415,7 @@ int call_check(pqh_ctx_t* ctx, bool have_src, long long n, const Call& c, bool* 
     if (c.nq > 0x7FFFFFFFll) return PQH_ERR_UNSUPPORTED;
     if (c.nq == 0 || n == 0 || c.nr == 0) {
         // (the fill has nothing to write: lims is the count's)
-        if (!c.fill) {
-            hipLaunchKernelGGL(radius_no_rows, dim3((unsigned)(c.nq / 256 + 1)), dim3(256), 0,
-                               ctx->stream, c.nq, c.lims);
-            PQH_LAUNCH_CHECK(ctx);
-        }
-        return PQH_OK;
+        return c.fill ? PQH_OK : pqh_range_no_rows_launch(ctx, c.nq, c.lims);
     }
     *run = true;
     return PQH_OK;
@@ -483,13 +478,8 @@ int scan_launch(pqh_ctx_t* ctx, int src, int nw, bool cx, RadiusArgs a, const Ca
     });
     if (rc) return rc;
     PQH_LAUNCH_CHECK(ctx);
-    if (!c.fill) {
-        const long long shares = g.groups * g.waves;
-        hipLaunchKernelGGL(radius_offsets, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream,
-                           a.plan + kHeaderWords, c.nq * shares, shares, c.nq, c.lims);
-        PQH_LAUNCH_CHECK(ctx);
-    }
-    return PQH_OK;
+    if (c.fill) return PQH_OK;
+    return pqh_range_offsets_launch(ctx, a.plan + kHeaderWords, g.groups * g.waves, c.nq, c.lims);
 }
 
 int range_stream(pqh_ctx_t* ctx, const pqh_tables_t* t, const unsigned char* d_stream,
@@ -522,6 +512,21 @@ int range_codes(pqh_ctx_t* ctx, const void* d_codes, long long n, int m, int k, 
 }
 
 }  // namespace
+
+int pqh_range_offsets_launch(pqh_ctx* ctx, long long* ent, long long shares, long long nq,
+                             long long* lims) {
+    hipLaunchKernelGGL(radius_offsets, dim3(1), dim3(64, kPlanWaves), 0, ctx->stream, ent,
+                       nq * shares, shares, nq, lims);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
+
+int pqh_range_no_rows_launch(pqh_ctx* ctx, long long nq, long long* lims) {
+    hipLaunchKernelGGL(radius_no_rows, dim3((unsigned)(nq / 256 + 1)), dim3(256), 0, ctx->stream,
+                       nq, lims);
+    PQH_LAUNCH_CHECK(ctx);
+    return PQH_OK;
+}
 
 extern "C" {
 
